@@ -13,13 +13,21 @@ log-scales, quaternions, opacity logits; 8.8 MB at cfg3) are restored from their
 step, inside the timed region, so the pair counts and kernel times do not drift as the scene trains and the
 result does not depend on --steps / --warmup.  Colours, texels and the Adam moments keep training.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
 
-Rank 0 prints ONE JSON line.  `value` = whole-job rendered+trained Mpix/s = N * H * W / (wall time / K).
-`roofline` prices the dominant raster kernel with SURVEY §8d's algorithmic bytes; `cpu_baseline` times the CPU
-oracle (oracle/, fp32 forward + autograd backward) on a bounded crop of the same view; `sub` holds the other
-configs' kernel times (cfg2 raster fwd+bwd, cfg1 forward), the eval render and a rechart.
+Rank 0 prints ONE JSON line.  `value` = whole-job rendered+trained Mpix/s = N * H * W / (wall time / K);
+`ms_per_step` = wall time / K in milliseconds.  A plain run sets up, warms up, times the K steps and prints the line.
+--dump-outputs DIR also writes what one step of the timed path produces, as DIR/<name>.npy, for comparing two builds
+output for output: after the timed region the last timed step is run once more, untimed, from the initial scene and a
+fresh optimizer state (the scene, cameras and targets are seeded, but the trained state is not reproducible: the
+gradient sums are float atomics, and Adam on random targets amplifies their rounding noise step by step, 1e-7 after
+25 steps, 1e-3 after 300), and its loss, image, gradients (texels included) and Adam first moments are written.
+--full adds everything that takes runs of its own: `roofline` prices the dominant raster kernel with
+SURVEY §8d's algorithmic bytes (a counting pass before the warmup, the forward's launch time from six steps after the
+timed region); `cpu_baseline` times the CPU oracle (oracle/, fp32 forward + autograd backward) on a bounded crop of
+the same view; `sub` holds the other configs' kernel times (cfg2 raster fwd+bwd, cfg1 forward), the eval render and a
+rechart.  Without --full those fields are null.
 """
 from __future__ import annotations
 
@@ -69,8 +77,15 @@ def parse():
     p.add_argument("--height", type=int, default=800)
     p.add_argument("--width", type=int, default=800)
     p.add_argument("--seed", type=int, default=42)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-sub", action="store_true", help="skip the cfg1/cfg2/eval/rechart sub-records")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: roofline (counting pass, forward-kernel "
+                        "steps), the cfg1/cfg2/cfg5/eval/rechart sub-records and the CPU-oracle baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step, run once more from the initial scene after the "
+                        "timed region (rank 0), as DIR/<name>.npy: float32, below 64 MB")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
+    p.add_argument("--no-sub", action="store_true",
+                   help="with --full: skip the cfg1/cfg2/cfg5/eval/rechart sub-records")
     p.add_argument("--no-defer-texture", action="store_true",
                    help="run the texel Adam update inside optimizer_step instead of deferring it into the next "
                         "step's render (GStexTrainer defer_texture)")
@@ -90,6 +105,22 @@ def algorithmic_bytes(nth, dims, H, W, C=3):
     fwd = 116 * Nv + 4 * I + 4 * C * Tv + 4 * (9 + C) * P + 8 * P
     bwd = 172 * Nv + 4 * I + 8 * C * Tv + 8 * P + 4 * (9 + C) * P
     return dict(N_v=Nv, I=I, T_v=Tv, P=P, fwd=fwd, bwd=bwd)
+
+
+@torch.no_grad()
+def counted_bytes(trainer, views, H, W):
+    """algorithmic_bytes of the trainer's scene, averaged over `views` (the geometry is stationary)."""
+    from gstex_amd import ops
+
+    quats = trainer.quats / trainer.quats.norm(dim=-1, keepdim=True)
+    s = torch.exp(trainer.scales[:, :-1])
+    scales = torch.cat([s, 1e-5 * s.mean(-1, keepdim=True)], -1)
+    abs_ = []
+    for v in views:
+        c, e = ops.get_aabb_2d(trainer.means, scales, 1, quats, v.viewmat, (v.fx, v.fy, v.cx, v.cy))
+        nth = ops.get_num_tiles_hit_2d(c, e, H, W, 16)
+        abs_.append(algorithmic_bytes(nth.cpu(), trainer.texture_dims.cpu(), H, W))
+    return {k: sum(a[k] for a in abs_) / len(abs_) for k in abs_[0]}
 
 
 def cpu_threads():
@@ -238,6 +269,108 @@ def eval_render_ms(trainer, view, reps):
     return statistics.median(_events_ms(times))
 
 
+def roofline_record(avg, ab):
+    """The dominant raster kernel (mean launch ms in `avg`) priced with the algorithmic bytes `ab` against the HBM
+    peak, next to the committed PMC traffic of that kernel."""
+    f_ms = avg.get("gstex_raster_fwd", float("nan"))
+    b_ms = avg.get("gstex_raster_bwd", float("nan"))
+    dom, dom_ms, dom_bytes = ("raster_bwd", b_ms, ab["bwd"]) if b_ms >= f_ms else ("raster_fwd", f_ms, ab["fwd"])
+    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
+    roofline = dict(bound="hbm", kernel=dom, achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit="GB/s",
+                    frac=round(achieved / HBM_PEAK_GBS, 4), traffic=None,
+                    traffic_source=f"profiles/{PROFILE_TAG}_traffic.json",
+                    bytes_per_launch=int(dom_bytes), launch_ms=round(dom_ms, 4),
+                    fwd_bwd_frac=round((ab["fwd"] + ab["bwd"]) / ((f_ms + b_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
+    prow = pmc_row(dom)
+    if prow is not None:
+        # 2 FETCH + WRITE: the gfx950 x2 FETCH_SIZE correction holds for vector loads of every width the kernels use
+        # but scalar loads count x1 (profiles/r03_fetch_calibration.json), so with the backward's scalar record reads
+        # this is an upper bound; FETCH + WRITE (all loads scalar) is the lower bound
+        roofline["traffic"] = int(prow["hbm_bytes_per_launch"])
+        if prow.get("fetch_kib") is not None and prow.get("write_kib") is not None:
+            roofline["traffic_lower_bound"] = int((prow["fetch_kib"] + prow["write_kib"]) * 1024)
+            roofline["traffic_calibration"] = "profiles/r03_fetch_calibration.json"
+        if prow.get("valu_insts"):
+            # the kernel is VALU-issue/latency bound, not HBM bound: its issue roofline, live time
+            roofline["valu_insts_per_launch"] = int(prow["valu_insts"])
+            roofline["valu_issue_frac"] = round(prow["valu_insts"] / (dom_ms * 1e-3 * 1024 * 2.4e9 / 2), 4)
+    return roofline
+
+
+DUMP_IMAGE_BYTES = 16 << 20  # --dump-outputs: the rendered image whole up to this size
+DUMP_ARRAY_BYTES = 3 << 20  # every other array whole up to this size (image + 14 arrays: 58 MiB at the most)
+
+
+def _rows_sample(t, cap, image=False):
+    """`t` as float32: whole, or above `cap` bytes a fixed sample of its rows (of its pixels for an H x W x C image;
+    a seeded draw that depends only on the shape, so two builds run with the same arguments keep the same rows)."""
+    t = t.detach()
+    if t.dim() == 0 or t.numel() * 4 <= cap:
+        return t.float().clone()
+    if image:
+        t = t.reshape(-1, t.shape[-1])
+    n = t.shape[0]
+    m = max(1, cap // (4 * (t.numel() // n)))
+    g = torch.Generator(device="cpu").manual_seed(0)
+    idx = torch.randint(0, n, (m,), generator=g).sort().values.to(t.device)
+    return t[idx].float()
+
+
+def reset_state(trainer, params0):
+    """The initial scene and a fresh optimizer state (every rank alike): what the dumped step starts from, so that its
+    outputs do not carry the run-to-run noise the earlier steps' float-atomic sums trained into the state."""
+    trainer.wait_texture()  # a pending deferred texel update first: it writes the texels and their moments
+    with torch.no_grad():
+        for p, p0 in zip(trainer.parameters(), params0):
+            p.copy_(p0)
+        for st in trainer.optimizer.state.values():
+            if torch.is_tensor(st["step"]):  # (torch.optim.Adam keeps a tensor, FusedAdam an int)
+                st["step"].zero_()
+            else:
+                st["step"] = 0
+            st["exp_avg"].zero_()
+            st["exp_avg_sq"].zero_()
+
+
+def dump_step(trainer, sync, params0, view, gt, sample=True):
+    """One step of the timed path (bench body: zero the gradients, forward_backward, optimizer_step) from
+    reset_state, and what it produces as device copies (written by write_outputs): the StepOutput of forward_backward
+    (loss, rendered image), the gradient backward left on every parameter group (the texels' in the trainer's sink)
+    and, after optimizer_step and the deferred texel update, Adam's first moment of every group -- from a fresh state
+    (1 - beta1) * g, which prices the Adam launches and the deferred update and stays well conditioned, where the
+    updated parameter itself, p - lr * g / (|g| + 1e-15), is the sign of g and flips wherever g is the rounding noise of
+    a cancelling float-atomic sum.  `sample` False (ranks > 0): run the step, keep nothing."""
+    reset_state(trainer, params0)
+    if sync is not None:
+        sync.zero()
+    else:
+        trainer.zero_grad()
+    out = trainer.forward_backward(view, gt)
+    arrays = {}
+    if sample:
+        arrays["loss"] = _rows_sample(out.loss, DUMP_ARRAY_BYTES)
+        arrays["rgb"] = _rows_sample(out.rgb, DUMP_IMAGE_BYTES, image=True)
+        for group, (p,) in trainer.param_groups().items():
+            if p.grad is not None:
+                arrays[f"grad_{group}"] = _rows_sample(p.grad, DUMP_ARRAY_BYTES)
+    trainer.optimizer_step(sync=sync)
+    trainer.wait_texture()
+    if sample:
+        for group, (p,) in trainer.param_groups().items():
+            st = trainer.optimizer.state.get(p)
+            if st:
+                arrays[f"adam_m_{group}"] = _rows_sample(st["exp_avg"], DUMP_ARRAY_BYTES)
+    return arrays
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -268,6 +401,8 @@ def main():
     g = torch.Generator(device="cpu").manual_seed(1000 + rank)
     gts = [torch.rand((H, W, 3), generator=g).to(dev) for _ in range(N_POSES)]
     geom0 = trainer.geometry_flat.detach().clone()  # means / log-scales / quats / opacity logits, one allocation
+    # --dump-outputs: the state the dumped step starts from (dump_step)
+    params0 = [p.detach().clone() for p in trainer.parameters()] if args.dump_outputs else None
     setup_s = time.perf_counter() - t_scene
     step_no = [0]
 
@@ -289,19 +424,12 @@ def main():
         step_no[0] += 1
         body(pose)
 
-    # counted quantities for the roofline (every pose of this rank's cycle; the geometry is stationary), before the
-    # warmup: host work between the warmup and the timed steps would idle the device and let its clock drop
-    with torch.no_grad():
-        quats = trainer.quats / trainer.quats.norm(dim=-1, keepdim=True)
-        s = torch.exp(trainer.scales[:, :-1])
-        scales = torch.cat([s, 1e-5 * s.mean(-1, keepdim=True)], -1)
-        abs_ = []
-        for pose in sorted({(rank + k * world) % N_POSES for k in range(args.steps)}):
-            v = views[pose]
-            c, e = ops.get_aabb_2d(trainer.means, scales, 1, quats, v.viewmat, (v.fx, v.fy, v.cx, v.cy))
-            nth = ops.get_num_tiles_hit_2d(c, e, H, W, 16)
-            abs_.append(algorithmic_bytes(nth.cpu(), trainer.texture_dims.cpu(), H, W))
-        ab = {k: sum(a[k] for a in abs_) / len(abs_) for k in abs_[0]}
+    # --full: counted quantities for the roofline (every pose of this rank's cycle; the geometry is stationary), before
+    # the warmup: host work between the warmup and the timed steps would idle the device and let its clock drop
+    ab = None
+    if args.full:
+        ab = counted_bytes(trainer, [views[p] for p in sorted({(rank + k * world) % N_POSES
+                                                                for k in range(args.steps)})], H, W)
 
     for w in range(args.warmup):
         if w == 1:
@@ -344,13 +472,14 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    last_pose = (rank + (step_no[0] - 1) * world) % N_POSES  # the last timed step's
     trainer.wait_texture()  # the last timed step's deferred texel update (the first timed step ran the warmup's)
     peak_mb = torch.cuda.max_memory_allocated(dev) / 2**20
     raster_ev = {n: ops._TIMING_EVENTS(n) for n in ("gstex_raster_fwd", "gstex_raster_bwd")}
     kt = ops.kernel_times()
     ops.set_kernel_timing(False)
     step_ms = _events_ms(list(zip(bound[:-1], bound[1:])))
-    if world == 1 and not args.no_kernel_timing:
+    if args.full and world == 1 and not args.no_kernel_timing:
         # the raster forward's launch time from a few untimed steps right after the timed region (same workload)
         ops.set_kernel_timing(True, names={"gstex_raster_fwd"})
         for _ in range(6):
@@ -358,6 +487,11 @@ def main():
         trainer.wait_texture()
         kt.update(ops.kernel_times())
         ops.set_kernel_timing(False)
+    dump = None
+    if params0 is not None and args.steps > 0:
+        # --dump-outputs: the last timed step once more, untimed, from the initial state (every rank runs it: its
+        # collectives); device copies now, written once the measurements are done
+        dump = dump_step(trainer, sync, params0, views[last_pose], gts[last_pose], sample=rank == 0)
     if world > 1:
         t = torch.tensor([elapsed], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -367,28 +501,7 @@ def main():
 
     avg = {k: sum(v) / len(v) for k, v in kt.items()}
     med = {k: statistics.median(v) for k, v in kt.items()}
-    f_ms = avg.get("gstex_raster_fwd", float("nan"))
-    b_ms = avg.get("gstex_raster_bwd", float("nan"))
-    dom, dom_ms, dom_bytes = ("raster_bwd", b_ms, ab["bwd"]) if b_ms >= f_ms else ("raster_fwd", f_ms, ab["fwd"])
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
-    roofline = dict(bound="hbm", kernel=dom, achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit="GB/s",
-                    frac=round(achieved / HBM_PEAK_GBS, 4), traffic=None,
-                    traffic_source=f"profiles/{PROFILE_TAG}_traffic.json",
-                    bytes_per_launch=int(dom_bytes), launch_ms=round(dom_ms, 4),
-                    fwd_bwd_frac=round((ab["fwd"] + ab["bwd"]) / ((f_ms + b_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
-    prow = pmc_row(dom)
-    if prow is not None:
-        # 2 FETCH + WRITE: the gfx950 x2 FETCH_SIZE correction holds for vector loads of every width the kernels use
-        # but scalar loads count x1 (profiles/r03_fetch_calibration.json), so with the backward's scalar record reads
-        # this is an upper bound; FETCH + WRITE (all loads scalar) is the lower bound
-        roofline["traffic"] = int(prow["hbm_bytes_per_launch"])
-        if prow.get("fetch_kib") is not None and prow.get("write_kib") is not None:
-            roofline["traffic_lower_bound"] = int((prow["fetch_kib"] + prow["write_kib"]) * 1024)
-            roofline["traffic_calibration"] = "profiles/r03_fetch_calibration.json"
-        if prow.get("valu_insts"):
-            # the kernel is VALU-issue/latency bound, not HBM bound: its issue roofline, live time
-            roofline["valu_insts_per_launch"] = int(prow["valu_insts"])
-            roofline["valu_issue_frac"] = round(prow["valu_insts"] / (dom_ms * 1e-3 * 1024 * 2.4e9 / 2), 4)
+    roofline = roofline_record(avg, ab) if ab is not None else None
 
     exchange = None
     if sync is not None and sync.phase_events and kt.get("gstex_raster_bwd") and kt.get("gstex_raster_fwd"):
@@ -413,7 +526,7 @@ def main():
                                  "bwd_end_to_next_fwd_ms minus the one-GPU gap (DESIGN.md §6)")
         sync.phase_events = None
     sub = None
-    if rank == 0 and world == 1 and not args.no_sub:
+    if args.full and rank == 0 and world == 1 and not args.no_sub:
         sub = {}
         # HBM footprint of the timed steps (torch allocator): resident state, and the peak including the step's
         # transient buffers (pair lists, records, per-pixel state, forward aux / checkpoints, gradients)
@@ -459,7 +572,7 @@ def main():
             dist.destroy_process_group()
         return
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         th = cpu_threads()
         try:
             cpu = cpu_baseline(make_scene(args.n_splats, args.n_texels, seed=args.seed), sphere_view(0, H, W),
@@ -474,6 +587,8 @@ def main():
                 sub["cfg2_fwd_bwd"]["cpu_oracle_128x128_crop_s"] = round(t2, 2)
         except Exception as ex:  # baseline must never kill the GPU result line
             cpu = dict(value=None, unit="Mpix/s", cores=th, kind="port", sample=f"failed: {ex!r}")
+    if dump is not None:
+        write_outputs(args.dump_outputs, dump)
     line = {
         "metric": "train-step ms + rendered Mpix/s, 200k splats/1e7 texels @800x800",
         "value": round(mpix, 4),
@@ -481,6 +596,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(ms, 4),
         "ms_per_step_median": round(statistics.median(step_ms), 4),
         "step_ms_events": [round(x, 3) for x in step_ms],  # rank 0's per-step HIP-event times
@@ -516,10 +632,11 @@ def main():
         "cpu_baseline": cpu,
         "kernel_ms": {k.replace("gstex_", ""): round(v, 4) for k, v in avg.items()},
         "kernel_ms_median": {k.replace("gstex_", ""): round(v, 4) for k, v in med.items()},
-        "counts": {k: int(ab[k]) for k in ("N_v", "I", "T_v", "P")},
+        "counts": {k: int(ab[k]) for k in ("N_v", "I", "T_v", "P")} if ab is not None else None,
         "sub": sub,
         "exchange": exchange,
         "setup_s": round(setup_s, 1),
+        "outputs": sorted(dump) if dump is not None else None,  # --dump-outputs: the <name>.npy files written
     }
     print(json.dumps(line), flush=True)
     if world > 1:

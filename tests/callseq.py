@@ -1,7 +1,9 @@
-"""Loader / replayer of the reference's recorded gstex_cuda call sequence (tests/golden/callseq.{json,npz}, made by
-tests/golden/make_callseq_golden.py from nerfstudio/models/gstex.py:992-1236 GStexModel.get_outputs)."""
+"""Loader / replayer of the reference's recorded gstex_cuda call sequence (tests/golden/callseq.json and
+callseq_<k>.npz, made by tests/golden/make_callseq_golden.py from nerfstudio/models/gstex.py:992-1236
+GStexModel.get_outputs)."""
 from __future__ import annotations
 
+import glob
 import json
 import os
 
@@ -21,9 +23,35 @@ IMPORTS = {
 }
 
 
+PART_BYTES = 768 << 10  # raw array bytes per callseq_<k>.npz: each committed part stays well below 1 MiB
+
+
+def save_arrays(arrays):
+    """The recorded tensors as tests/golden/callseq_<k>.npz, in key order, a new part whenever the next array would
+    take the current one above PART_BYTES.  Returns the paths written."""
+    for old in glob.glob(os.path.join(GOLDEN, "callseq_[0-9]*.npz")):
+        os.remove(old)
+    parts, size = [{}], 0
+    for k, v in arrays.items():
+        if parts[-1] and size + v.nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += v.nbytes
+    paths = [os.path.join(GOLDEN, f"callseq_{i:02d}.npz") for i in range(len(parts))]
+    for path, part in zip(paths, parts):
+        np.savez_compressed(path, **part)
+    return paths
+
+
 def load():
     meta = json.load(open(os.path.join(GOLDEN, "callseq.json")))
-    arrays = dict(np.load(os.path.join(GOLDEN, "callseq.npz")))
+    arrays = {}
+    paths = sorted(glob.glob(os.path.join(GOLDEN, "callseq_[0-9]*.npz")))
+    assert len(paths) == meta["npz_parts"], f"callseq.json names {meta['npz_parts']} npz parts, found {paths}"
+    for path in paths:
+        with np.load(path, allow_pickle=False) as z:
+            arrays.update({k: z[k] for k in z.files})
     return meta, arrays
 
 

@@ -5,7 +5,7 @@ Run in the build container only (reads /root/reference, which the GPU box does n
     python tests/golden/make_callseq_golden.py
 Writes tests/golden/callseq.json (the calls: function, positional / keyword structure, Python scalar types, tensor
 dtypes / shapes / contiguity / requires_grad, and which argument is which earlier call's output) and
-tests/golden/callseq.npz (the seeded input tensors and the expected outputs).
+tests/golden/callseq_<k>.npz (the seeded input tensors and the expected outputs, in parts below 1 MiB each).
 
 GStexModel.get_outputs (nerfstudio/models/gstex.py:992-1236) is AST-extracted from the source text and exec'd
 UNCHANGED with a stub `self` (the model's parameters: a seeded gstex_amd.scene.make_scene, charts from build_charts),
@@ -38,7 +38,6 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 REF = "/root/reference/nerfstudio/models/gstex.py"
 OUT_JSON = os.path.join(HERE, "callseq.json")
-OUT_NPZ = os.path.join(HERE, "callseq.npz")
 
 N_SPLATS, N_TEXELS, H, W, SEED = 300, 4000, 64, 64, 7
 
@@ -266,9 +265,12 @@ def main():
             if isinstance(v, torch.Tensor):
                 arrays[f"{scenario}/images/{k}"] = v.detach().cpu().numpy()
         print(scenario, [c["fn"] for c in rec.calls], sorted(images))
+    from callseq import save_arrays
+
+    parts = save_arrays(arrays)
+    meta["npz_parts"] = len(parts)  # callseq.load() refuses a tree that lost one
     json.dump(meta, open(OUT_JSON, "w"), indent=1)
-    np.savez_compressed(OUT_NPZ, **arrays)
-    print("wrote", OUT_JSON, OUT_NPZ, sum(a.nbytes for a in arrays.values()) / 1e6, "MB raw")
+    print("wrote", OUT_JSON, *parts, sum(a.nbytes for a in arrays.values()) / 1e6, "MB raw")
 
 
 if __name__ == "__main__":

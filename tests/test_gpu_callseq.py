@@ -1,8 +1,8 @@
 """GPU replay of the reference's own gstex_cuda call sequence.
 
-tests/golden/callseq.{json,npz} hold every call nerfstudio/models/gstex.py:992-1236 (GStexModel.get_outputs) makes
-into gstex_cuda in three modes -- training, the eval render (extra_stuff: three 6-channel calls, the last with
-settings | 1 << 15) and the viewer's cached path -- recorded with its exact argument structure (positional order, the
+tests/golden/callseq.json and callseq_<k>.npz hold every call nerfstudio/models/gstex.py:992-1236
+(GStexModel.get_outputs) makes into gstex_cuda in three modes -- training, the eval render (extra_stuff: three
+6-channel calls, the last with settings | 1 << 15) and the viewer's cached path -- recorded with its exact argument structure (positional order, the
 int 1 glob_scale, viewmat.squeeze()[:3, :], the non-contiguous c2w = viewmat.inverse(), texture_info, the
 background=zeros_like / use_torch_impl=False keywords) and the seeded inputs.  Here each call is made again, in order,
 through the real gstex_cuda shim on the GPU, functions resolved from the modules the reference imports them from;

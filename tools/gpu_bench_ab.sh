@@ -7,7 +7,7 @@ OUT=gpurun_out/$TAG; mkdir -p $OUT
 for r in $(seq 1 $R); do
   for x in A B; do
     if [ $x = A ]; then args=$A; else args=$B; fi
-    timeout -k 10 300 python3 -u bench.py --steps 20 --warmup 5 $args > $OUT/bench_${x}_$r.log 2>&1 || { tail -20 $OUT/bench_${x}_$r.log; exit 1; }
+    timeout -k 10 300 python3 -u bench.py --steps 20 --warmup 5 --full $args > $OUT/bench_${x}_$r.log 2>&1 || { tail -20 $OUT/bench_${x}_$r.log; exit 1; }
     python3 - $OUT/bench_${x}_$r.log "$x: $args" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -14,7 +14,7 @@ for f in 0 1; do
 done
 for r in $(seq 1 ${ROUNDS:-2}); do
   for f in 0 1; do
-    GSTEX_FUSED_STEP=$f timeout -k 10 300 python3 -u bench.py --steps 20 --warmup 5 > $OUT/bench_${f}_$r.log 2>&1 || { tail -20 $OUT/bench_${f}_$r.log; exit 1; }
+    GSTEX_FUSED_STEP=$f timeout -k 10 300 python3 -u bench.py --steps 20 --warmup 5 --full > $OUT/bench_${f}_$r.log 2>&1 || { tail -20 $OUT/bench_${f}_$r.log; exit 1; }
     python3 - $OUT/bench_${f}_$r.log $f <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

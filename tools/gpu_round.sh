@@ -12,9 +12,9 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
   tail -1 $OUT/smoke.log
 fi
-timeout -k 10 400 python3 -u bench.py > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
+timeout -k 10 400 python3 -u bench.py --full > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log | cut -c1-300
-timeout -k 10 300 python3 -u bench.py --steps 20 --warmup 5 > $OUT/bench_driver_cmd.log 2>&1 || { tail -20 $OUT/bench_driver_cmd.log; exit 1; }
+timeout -k 10 300 python3 -u bench.py --steps 20 --warmup 5 --full > $OUT/bench_driver_cmd.log 2>&1 || { tail -20 $OUT/bench_driver_cmd.log; exit 1; }
 tail -1 $OUT/bench_driver_cmd.log | cut -c1-200
 if [ -z "$SKIP_PROF" ]; then
   timeout -k 10 1200 bash tools/profile_bench.sh $TAG > $OUT/prof.log 2>&1 || { tail -20 $OUT/prof.log; exit 1; }
