@@ -16,7 +16,7 @@ import torch  # noqa: F401  (load torch's HIP runtime first)
 
 LIB_PATH = os.environ.get("GSTEX_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgstex_hip.so")
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 REC_FLOATS = 32
 HP_DOUBLES = 12  # GSTEX_HP_DOUBLES: the fp64 row of a near-edge-on splat (gstex_raster_setup hp_records)
 PARTIAL_FLOATS = 32  # GSTEX_PARTIAL_FLOATS: floats between partial rows of a backward with geometry gradients
@@ -25,7 +25,6 @@ SETTING_AA_BLUR = 1 << 9
 SETTING_DIST_REG = 1 << 10
 SETTING_EDIT = 1 << 13
 SETTING_EVAL_NORMAL = 1 << 15
-SETTING_AUX_ZEROED = 1 << 28  # GSTEX_SETTING_AUX_ZEROED: the prologue zeroed the forward's accumulated aux span
 
 
 class GstexCamera(ctypes.Structure):
@@ -89,8 +88,45 @@ class GstexTrainEpilogueArgs(ctypes.Structure):
             "v_features_rest", "v_scales_act", "v_quats_n", "v_rgbs", "v_opacities_act", "v_centers", "v_uv0")]
 
 
+class GstexRasterScene(ctypes.Structure):
+    """gstex_raster_scene (ABI 19): what the raster forward and its backward share."""
+    _fields_ = [("cam", GstexCamera), ("channels", c_int32), ("settings", c_int32)] + [
+        (name, c_void_p) for name in (
+            "background", "records", "hp_records", "tile_ranges", "sorted_ids", "texture")] + [
+        ("n_texels", c_int64), ("tex_scale", c_float), ("tex_bias", c_float), ("state", c_void_p),
+        ("n_isect", c_int64), ("aux", c_void_p)]
+
+
+class GstexRasterFwdArgs(ctypes.Structure):
+    """gstex_raster_fwd_args (ABI 19)."""
+    _fields_ = [("scene", GstexRasterScene)] + [
+        (name, c_void_p) for name in (
+            "tile_order", "out_img", "out_depth", "out_reg", "out_alpha", "out_tex", "out_normal")] + [
+        ("zero_buf", c_void_p), ("zero_floats", c_int64), ("zero_buf2", c_void_p), ("zero_floats2", c_int64),
+        ("aux_zeroed", c_int32)]
+
+
+class GstexRasterBwdArgs(ctypes.Structure):
+    """gstex_raster_bwd_args (ABI 19)."""
+    _fields_ = [("scene", GstexRasterScene)] + [
+        (name, c_void_p) for name in (
+            "sorted_slots", "v_img", "v_depth", "v_reg", "v_alpha", "v_tex", "v_normal", "partials", "row_flags",
+            "v_texture")] + [("zero_buf", c_void_p), ("zero_floats", c_int64)]
+
+
+class GstexRasterSetupBwdArgs(ctypes.Structure):
+    """gstex_raster_setup_bwd_args (ABI 19)."""
+    _fields_ = [("n", c_int32), ("glob_scale", c_float), ("row_floats", c_int32), ("fold_aabb", c_int32),
+                ("n_rows", c_int64), ("cam", GstexCamera)] + [
+        (name, c_void_p) for name in (
+            "means", "scales", "quats", "umap", "vmap", "num_tiles_hit", "offsets", "partials", "row_flags",
+            "v_means", "v_scales", "v_quats", "v_rgbs", "v_opacities", "v_centers", "v_uv0")]
+
+
 ADAM_ZERO_GRAD = 1  # GSTEX_ADAM_ZERO_GRAD
 ADAM_GRID_SHIFT = 8  # GSTEX_ADAM_GRID_SHIFT
+BIN_CAPPED = 1  # GSTEX_BIN_CAPPED
+BIN_COUNT_ZEROED = 2  # GSTEX_BIN_COUNT_ZEROED
 _P = c_void_p
 _CAM = POINTER(GstexCamera)
 
@@ -105,22 +141,13 @@ SIGNATURES = {
     "gstex_num_tiles_hit": (c_int32, [c_int32, _P, _P, c_int32, c_int32, c_int32, _P, _P]),
     "gstex_preprocess": (c_int32, [c_int32, _P, _P, c_float, _P, _CAM, _P, _P, _P, _P, _P]),
     "gstex_scan_workspace_size": (c_size_t, [c_int32]),
-    "gstex_scan_offsets": (c_int32, [c_int32, _P, _P, _P, c_size_t, _P]),
+    "gstex_scan_offsets": (c_int32, [c_int32, _P, _P, _P, c_size_t, POINTER(GstexPairGuard), _P]),
     "gstex_bin_workspace_size": (c_size_t, [c_int32, c_int64, c_int32]),
     "gstex_bin_sort": (
         c_int32,
-        [c_int32, c_int64, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_size_t, _P],
-    ),
-    "gstex_bin_sort_ordered": (
-        c_int32,
-        [c_int32, c_int64, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_size_t, _P],
+        [c_int32, c_int64, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, c_size_t, _P],
     ),
     "gstex_tile_order": (c_int32, [c_int32, _P, _P, _P]),
-    "gstex_scan_offsets_guarded": (c_int32, [c_int32, _P, _P, _P, c_size_t, POINTER(GstexPairGuard), _P]),
-    "gstex_bin_sort_capped": (
-        c_int32,
-        [c_int32, c_int64, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_size_t, _P],
-    ),
     "gstex_host_words_alloc": (c_int32, [c_int32, POINTER(c_void_p), POINTER(c_void_p)]),
     "gstex_host_words_free": (c_int32, [c_void_p]),
     "gstex_event_create": (c_int32, [c_int32, POINTER(c_void_p)]),
@@ -132,39 +159,12 @@ SIGNATURES = {
         c_int32,
         [c_int32, _P, _P, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _CAM, _P, _P, _P],
     ),
-    "gstex_raster_fwd": (
-        c_int32,
-        [_CAM, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int64, c_float, c_float, _P, _P, _P, _P, _P, _P, _P,
-         c_int64, _P, _P],
-    ),
-    "gstex_raster_fwd_zero": (
-        c_int32,
-        [_CAM, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int64, c_float, c_float, _P, _P, _P, _P, _P, _P, _P,
-         c_int64, _P, _P, c_int64, _P, c_int64, _P],
-    ),
+    "gstex_raster_fwd": (c_int32, [POINTER(GstexRasterFwdArgs), _P]),
     "gstex_raster_aux_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "gstex_unit_order": (c_int32, [c_int32, _P, _P, _P, _P]),
     "gstex_unit_order_scratch_words": (c_size_t, []),
-    "gstex_raster_bwd": (
-        c_int32,
-        [_CAM, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int64, c_float, c_float, _P, _P, _P, _P, _P, _P, _P,
-         c_int64, _P, _P, _P, _P, _P],
-    ),
-    "gstex_raster_bwd_zero": (
-        c_int32,
-        [_CAM, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int64, c_float, c_float, _P, _P, _P, _P, _P, _P, _P,
-         c_int64, _P, _P, _P, _P, _P, c_int64, _P],
-    ),
-    "gstex_raster_setup_bwd": (
-        c_int32,
-        [c_int32, _P, _P, c_float, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int64, _CAM, _P, _P, _P, _P, _P, _P, _P,
-         _P],
-    ),
-    "gstex_raster_setup_bwd_aabb": (
-        c_int32,
-        [c_int32, _P, _P, c_float, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int64, _CAM, _P, _P, _P, _P, _P, _P, _P,
-         _P],
-    ),
+    "gstex_raster_bwd": (c_int32, [POINTER(GstexRasterBwdArgs), _P]),
+    "gstex_raster_setup_bwd": (c_int32, [POINTER(GstexRasterSetupBwdArgs), _P]),
     "gstex_sh_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "gstex_sh_bwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "gstex_texture_sample": (c_int32, [c_int64, c_int32, _P, _P, c_int64, _P, _P, _P]),
@@ -179,12 +179,8 @@ SIGNATURES = {
                                  _P, c_size_t, _P]),
     "gstex_loss_bwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, POINTER(c_float), c_float, _P, _P,
                                  _P, _P, _P, c_size_t, _P]),
-    "gstex_adam_step": (c_int32, [c_int32, POINTER(GstexAdamTensor), c_double, c_double, c_double, _P]),
-    "gstex_adam_step_ex": (c_int32, [c_int32, POINTER(GstexAdamTensor), c_double, c_double, c_double, c_int32, _P]),
-    "gstex_adam_step_scaled": (c_int32, [c_int32, POINTER(GstexAdamTensor), c_double, c_double, c_double, c_int32,
-                                         c_float, _P]),
-    "gstex_adam_step_guarded": (c_int32, [c_int32, POINTER(GstexAdamTensor), c_double, c_double, c_double, c_int32,
-                                          c_float, _P, _P]),
+    "gstex_adam_step": (c_int32, [c_int32, POINTER(GstexAdamTensor), c_double, c_double, c_double, c_int32, c_float,
+                                  _P, _P]),
     "gstex_train_prologue": (c_int32, [POINTER(GstexTrainPrologueArgs), _P]),
     "gstex_train_prologue_scan_bytes": (c_size_t, [c_int32]),
     "gstex_train_epilogue": (c_int32, [POINTER(GstexTrainEpilogueArgs), _P]),

@@ -47,8 +47,8 @@ struct AdamArgs {
     int64_t block_start[kAdamMaxTensors + 1];
     int n;
     float beta1, beta2, eps, one_m_beta1, one_m_beta2;
-    float gscale;  // gradient scale applied on read (gstex_adam_step_scaled: a data-parallel 1 / world), 1 = none
-    const float* skip;  // gstex_adam_step_guarded: nothing is updated when *skip != 0 (nullable)
+    float gscale;  // gradient scale applied on read (grad_scale: a data-parallel 1 / world), 1 = none
+    const float* skip;  // skip: nothing is updated when *skip != 0 (nullable)
 };
 
 template <bool SCALE>
@@ -129,9 +129,12 @@ __global__ __launch_bounds__(kAdamThreads) void adam_kernel(const AdamArgs a) {
 
 }  // namespace
 
-namespace {
-int adam_launch(int32_t n_tensors, const gstex_adam_tensor* tensors, double beta1, double beta2, double eps,
-                int32_t flags, float grad_scale, void* stream, const float* skip = nullptr) {
+extern "C" int gstex_adam_step(int32_t n_tensors, const gstex_adam_tensor* tensors, double beta1, double beta2,
+                               double eps, int32_t flags, float grad_scale, const float* skip, void* stream) {
+    GSTEX_REQUIRE((flags & ~(GSTEX_ADAM_ZERO_GRAD | (0xFFFF << GSTEX_ADAM_GRID_SHIFT))) == 0,
+                  "gstex_adam_step: unknown flags 0x%x", flags);
+    GSTEX_REQUIRE(grad_scale == grad_scale && grad_scale > 0.0f && grad_scale <= 1.0f,
+                  "gstex_adam_step: grad_scale must be in (0, 1] (got %g)", (double)grad_scale);
     GSTEX_REQUIRE(n_tensors >= 0 && n_tensors <= kAdamMaxTensors,
                   "gstex_adam_step: n_tensors must be in [0, %d] (got %d)", kAdamMaxTensors, n_tensors);
     GSTEX_REQUIRE(n_tensors == 0 || tensors, "gstex_adam_step: null tensor table");
@@ -168,35 +171,4 @@ int adam_launch(int32_t n_tensors, const gstex_adam_tensor* tensors, double beta
     else if (sc) adam_kernel<false, true><<<grid, kAdamThreads, 0, st>>>(a);
     else adam_kernel<false, false><<<grid, kAdamThreads, 0, st>>>(a);
     return gstex::launch_status("gstex_adam_step");
-}
-}  // namespace
-
-extern "C" int gstex_adam_step(int32_t n_tensors, const gstex_adam_tensor* tensors, double beta1, double beta2,
-                               double eps, void* stream) {
-    return adam_launch(n_tensors, tensors, beta1, beta2, eps, 0, 1.0f, stream);
-}
-
-extern "C" int gstex_adam_step_ex(int32_t n_tensors, const gstex_adam_tensor* tensors, double beta1, double beta2,
-                                  double eps, int32_t flags, void* stream) {
-    GSTEX_REQUIRE((flags & ~(GSTEX_ADAM_ZERO_GRAD | (0xFFFF << GSTEX_ADAM_GRID_SHIFT))) == 0,
-                  "gstex_adam_step_ex: unknown flags 0x%x", flags);
-    return adam_launch(n_tensors, tensors, beta1, beta2, eps, flags, 1.0f, stream);
-}
-
-extern "C" int gstex_adam_step_scaled(int32_t n_tensors, const gstex_adam_tensor* tensors, double beta1, double beta2,
-                                      double eps, int32_t flags, float grad_scale, void* stream) {
-    GSTEX_REQUIRE((flags & ~(GSTEX_ADAM_ZERO_GRAD | (0xFFFF << GSTEX_ADAM_GRID_SHIFT))) == 0,
-                  "gstex_adam_step_scaled: unknown flags 0x%x", flags);
-    GSTEX_REQUIRE(grad_scale == grad_scale && grad_scale > 0.0f && grad_scale <= 1.0f,
-                  "gstex_adam_step_scaled: grad_scale must be in (0, 1] (got %g)", (double)grad_scale);
-    return adam_launch(n_tensors, tensors, beta1, beta2, eps, flags, grad_scale, stream);
-}
-
-extern "C" int gstex_adam_step_guarded(int32_t n_tensors, const gstex_adam_tensor* tensors, double beta1, double beta2,
-                                       double eps, int32_t flags, float grad_scale, const float* skip, void* stream) {
-    GSTEX_REQUIRE((flags & ~(GSTEX_ADAM_ZERO_GRAD | (0xFFFF << GSTEX_ADAM_GRID_SHIFT))) == 0,
-                  "gstex_adam_step_guarded: unknown flags 0x%x", flags);
-    GSTEX_REQUIRE(grad_scale == grad_scale && grad_scale > 0.0f && grad_scale <= 1.0f,
-                  "gstex_adam_step_guarded: grad_scale must be in (0, 1] (got %g)", (double)grad_scale);
-    return adam_launch(n_tensors, tensors, beta1, beta2, eps, flags, grad_scale, stream, skip);
 }

@@ -127,9 +127,9 @@ int run_scan(int n, const int32_t* in, int32_t* out, int32_t* block_sums, hipStr
 size_t scan_ws_bytes(int n) { return (size_t)(div_up(n, kScanTile) + 1) * sizeof(int32_t); }
 
 // 1. count + rank
-// Capacity mode (gstex_bin_sort_capped): the pair total offsets[n] is read on the device; a total beyond the pair
+// Capacity mode (GSTEX_BIN_CAPPED): the pair total offsets[n] is read on the device; a total beyond the pair
 // buffers' capacity leaves every tile empty (no pair is emitted, so nothing is written past the buffers) and the
-// step's guard flag (gstex_scan_offsets_guarded) tells the optimizer to skip the step.
+// step's guard flag (gstex_scan_offsets with a guard) tells the optimizer to skip the step.
 __device__ __forceinline__ bool over_capacity(const int32_t* offsets, int n, long long cap) {
     return cap >= 0 && (long long)offsets[n] > cap;
 }
@@ -595,11 +595,14 @@ size_t bin_layout(int n_tiles, int64_t n_isect, char* base, BinWorkspace* ws) {
 extern "C" size_t gstex_scan_workspace_size(int32_t n) { return scan_ws_bytes(n < 0 ? 0 : n); }
 
 extern "C" int gstex_scan_offsets(int32_t n, const int32_t* num_tiles_hit, int32_t* offsets, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+                                  size_t workspace_bytes, const gstex_pair_guard* guard, void* stream) {
+    GSTEX_REQUIRE(!guard || guard->capacity >= 0, "gstex_scan_offsets: capacity < 0");
     GSTEX_REQUIRE(n >= 0 && offsets, "gstex_scan_offsets: invalid arguments");
     GSTEX_REQUIRE(n == 0 || num_tiles_hit, "gstex_scan_offsets: null input");
     GSTEX_REQUIRE(workspace_bytes >= scan_ws_bytes(n) && workspace, "gstex_scan_offsets: workspace too small");
-    return run_scan(n, num_tiles_hit, offsets, (int32_t*)workspace, as_stream(stream));
+    if (!guard) return run_scan(n, num_tiles_hit, offsets, (int32_t*)workspace, as_stream(stream));
+    const ScanGuard g{(long long)guard->capacity, guard->step_flag, guard->host_count, guard->first ? 1 : 0};
+    return run_scan(n, num_tiles_hit, offsets, (int32_t*)workspace, as_stream(stream), g);
 }
 
 extern "C" size_t gstex_bin_workspace_size(int32_t n, int64_t n_isect, int32_t n_tiles) {
@@ -607,15 +610,19 @@ extern "C" size_t gstex_bin_workspace_size(int32_t n, int64_t n_isect, int32_t n
     return bin_layout(n_tiles, n_isect, nullptr, nullptr);
 }
 
-namespace {
 // tile_order_out (nullable): the largest-first launch order the tile sort used, identical to what
 // gstex_tile_order computes from tile_ranges (both rank the same bucket sizes), so the forward reuses it
-// capped: n_isect is the pair buffers' capacity and the true total is read on the device (offsets[n]; above the
-// capacity every tile comes out empty) -- no host read-back of the total is needed to launch the binning
-int bin_sort_impl(int32_t n, int64_t n_isect, const float* centers, const float* extents, const float* depths,
-                  const int32_t* offsets, int32_t H, int32_t W, int32_t block, int32_t* tile_ranges,
-                  int32_t* sorted_ids, int32_t* sorted_slots, int32_t* tile_order_out, void* workspace,
-                  size_t workspace_bytes, void* stream, bool capped = false, bool count_zeroed = false) {
+// GSTEX_BIN_CAPPED: n_isect is the pair buffers' capacity and the true total is read on the device (offsets[n]; above
+// the capacity every tile comes out empty) -- no host read-back of the total is needed to launch the binning
+extern "C" int gstex_bin_sort(int32_t n, int64_t n_isect, const float* centers, const float* extents,
+                              const float* depths, const int32_t* offsets, int32_t H, int32_t W, int32_t block,
+                              int32_t* tile_ranges, int32_t* sorted_ids, int32_t* sorted_slots,
+                              int32_t* tile_order_out, int32_t flags, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    GSTEX_REQUIRE((flags & ~(GSTEX_BIN_CAPPED | GSTEX_BIN_COUNT_ZEROED)) == 0, "gstex_bin_sort: unknown flags 0x%x",
+                  flags);
+    const bool capped = flags & GSTEX_BIN_CAPPED, count_zeroed = flags & GSTEX_BIN_COUNT_ZEROED;
+    GSTEX_REQUIRE(!capped || tile_order_out, "gstex_bin_sort: null tile_order (GSTEX_BIN_CAPPED needs one)");
     GSTEX_REQUIRE(n >= 0 && n_isect >= 0 && n_isect < (1ll << 31) && H > 0 && W > 0 && block > 0,
                   "gstex_bin_sort: invalid sizes (n=%d, n_isect=%lld, H=%d, W=%d, block=%d)", n,
                   (long long)n_isect, H, W, block);
@@ -660,39 +667,6 @@ int bin_sort_impl(int32_t n, int64_t n_isect, const float* centers, const float*
                                                        sorted_slots);
     return launch_status("gstex_bin_sort");
 }
-}  // namespace
-
-extern "C" int gstex_bin_sort(int32_t n, int64_t n_isect, const float* centers, const float* extents,
-                              const float* depths, const int32_t* num_tiles_hit, const int32_t* offsets,
-                              int32_t H, int32_t W, int32_t block, int32_t* tile_ranges, int32_t* sorted_ids,
-                              int32_t* sorted_slots, void* workspace, size_t workspace_bytes, void* stream) {
-    (void)num_tiles_hit;
-    return bin_sort_impl(n, n_isect, centers, extents, depths, offsets, H, W, block, tile_ranges, sorted_ids,
-                         sorted_slots, nullptr, workspace, workspace_bytes, stream);
-}
-
-extern "C" int gstex_bin_sort_ordered(int32_t n, int64_t n_isect, const float* centers, const float* extents,
-                                      const float* depths, const int32_t* num_tiles_hit, const int32_t* offsets,
-                                      int32_t H, int32_t W, int32_t block, int32_t* tile_ranges,
-                                      int32_t* sorted_ids, int32_t* sorted_slots, int32_t* tile_order,
-                                      void* workspace, size_t workspace_bytes, void* stream) {
-    (void)num_tiles_hit;
-    GSTEX_REQUIRE(tile_order, "gstex_bin_sort_ordered: null tile_order");
-    return bin_sort_impl(n, n_isect, centers, extents, depths, offsets, H, W, block, tile_ranges, sorted_ids,
-                         sorted_slots, tile_order, workspace, workspace_bytes, stream);
-}
-
-extern "C" int gstex_bin_sort_capped(int32_t n, int64_t capacity, const float* centers, const float* extents,
-                                     const float* depths, const int32_t* num_tiles_hit, const int32_t* offsets,
-                                     int32_t H, int32_t W, int32_t block, int32_t* tile_ranges, int32_t* sorted_ids,
-                                     int32_t* sorted_slots, int32_t* tile_order, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
-    (void)num_tiles_hit;
-    GSTEX_REQUIRE(tile_order, "gstex_bin_sort_capped: null tile_order");
-    GSTEX_REQUIRE(capacity >= 0, "gstex_bin_sort_capped: capacity < 0");
-    return bin_sort_impl(n, capacity, centers, extents, depths, offsets, H, W, block, tile_ranges, sorted_ids,
-                         sorted_slots, tile_order, workspace, workspace_bytes, stream, true);
-}
 
 namespace gstex {
 ZeroSpan bin_count_span(void* workspace, int32_t n_tiles, int64_t n_isect) {
@@ -700,27 +674,7 @@ ZeroSpan bin_count_span(void* workspace, int32_t n_tiles, int64_t n_isect) {
     bin_layout(n_tiles, n_isect, (char*)workspace, &ws);
     return ZeroSpan{ws.tile_count, align256((size_t)(n_tiles + 1) * sizeof(int32_t))};
 }
-
-int bin_sort_capped_prezeroed(int32_t n, int64_t capacity, const float* centers, const float* extents,
-                              const float* depths, const int32_t* offsets, int32_t H, int32_t W, int32_t block,
-                              int32_t* tile_ranges, int32_t* sorted_ids, int32_t* sorted_slots, int32_t* tile_order,
-                              void* workspace, size_t workspace_bytes, void* stream) {
-    GSTEX_REQUIRE(tile_order, "gstex_bin_sort_capped: null tile_order");
-    GSTEX_REQUIRE(capacity >= 0, "gstex_bin_sort_capped: capacity < 0");
-    return bin_sort_impl(n, capacity, centers, extents, depths, offsets, H, W, block, tile_ranges, sorted_ids,
-                         sorted_slots, tile_order, workspace, workspace_bytes, stream, true, true);
-}
 }  // namespace gstex
-
-extern "C" int gstex_scan_offsets_guarded(int32_t n, const int32_t* num_tiles_hit, int32_t* offsets, void* workspace,
-                                          size_t workspace_bytes, const gstex_pair_guard* guard, void* stream) {
-    GSTEX_REQUIRE(n >= 0 && offsets && guard, "gstex_scan_offsets_guarded: invalid arguments");
-    GSTEX_REQUIRE(n == 0 || num_tiles_hit, "gstex_scan_offsets_guarded: null input");
-    GSTEX_REQUIRE(workspace_bytes >= scan_ws_bytes(n) && workspace, "gstex_scan_offsets_guarded: workspace too small");
-    GSTEX_REQUIRE(guard->capacity >= 0, "gstex_scan_offsets_guarded: capacity < 0");
-    const ScanGuard g{(long long)guard->capacity, guard->step_flag, guard->host_count, guard->first ? 1 : 0};
-    return run_scan(n, num_tiles_hit, offsets, (int32_t*)workspace, as_stream(stream), g);
-}
 
 extern "C" int gstex_tile_order(int32_t n_tiles, const int32_t* tile_ranges, int32_t* tile_order, void* stream) {
     GSTEX_REQUIRE(n_tiles >= 0, "gstex_tile_order: invalid n_tiles %d", n_tiles);

@@ -34,7 +34,7 @@ extern "C" const char* gstex_last_error(void) { return gstex::g_last_error.c_str
 extern "C" int gstex_abi_version(void) { return GSTEX_ABI_VERSION; }
 
 // Device-writable host words (ABI 13): the pair-capacity guard writes each render's pair total into one of them
-// (gstex_scan_offsets_guarded), the host reads it after the stream has passed the scan -- no copy, no sync.
+// (gstex_scan_offsets with a guard), the host reads it after the stream has passed the scan -- no copy, no sync.
 extern "C" int gstex_host_words_alloc(int32_t n, int32_t** host, int32_t** device) {
     if (n <= 0 || !host || !device) {
         gstex::set_error("gstex_host_words_alloc: invalid arguments");

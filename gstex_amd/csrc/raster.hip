@@ -210,9 +210,10 @@ struct AuxPtrs {
     int F;
 };
 struct AuxLayout { size_t masks, cost, order, order_ws, slot_tile, ckpt, bytes; int64_t n_slots, n_units; int F; };
-struct ZeroBufs { float* p[2]; int64_t n[2]; };  // buffers the forward's grid zeroes (gstex_raster_fwd_zero)
-// The accumulation buffers a raster kernel's whole grid zeroes as a side job (gstex_raster_fwd_zero: the texel gradient
-// and the splat-gradient sums of the backward that follows; gstex_raster_bwd_zero: the next step's texel gradient):
+struct ZeroBufs { float* p[2]; int64_t n[2]; };  // buffers a raster grid zeroes (zero_buf of gstex_raster_fwd / _bwd)
+// The accumulation buffers a raster kernel's whole grid zeroes as a side job (gstex_raster_fwd's zero_buf / zero_buf2:
+// the texel gradient and the splat-gradient sums of the backward that follows; gstex_raster_bwd's zero_buf: the next
+// step's texel gradient):
 // plain streaming stores the VALU-bound raster kernels hide, instead of fill passes (or an Adam update's zero stores)
 __device__ __forceinline__ void zero_bufs(const ZeroBufs& zb) {
     const int64_t nthr = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1426,7 +1427,7 @@ constexpr int kSumSlots = GSTEX_SUM_SLOTS;  // slots whose rows one lane group h
 // order and writes the 32 sums over the splat's first row (slot offsets[g], quadrant 0), whose values it has already
 // read -- no other splat reads that row; then setup_bwd_chain_kernel, one thread per splat, chains the sums to the
 // parameters.  (One fused kernel, 40 splats per workgroup, measured 120 vs 102 us in round 2.)
-// Capacity mode (n_rows >= 0, gstex_bin_sort_capped): a total offsets[n] above the row capacity means the binning
+// Capacity mode (n_rows >= 0, GSTEX_BIN_CAPPED): a total offsets[n] above the row capacity means the binning
 // left every tile empty and no row was written; both kernels then treat every splat as pair-free (zero gradients)
 // instead of addressing rows past the buffers.
 // 32 lanes per splat: lane 8 q + m reads float4 m (columns 4m .. 4m+3) of the quadrant-q rows, kSumSlots slots at a
@@ -1704,7 +1705,7 @@ int check_settings(int settings) {
 // The training render's backward after the raster backward, one thread per splat (gstex_train_epilogue, ABI 17): the
 // record chain of setup_bwd_chain_kernel<true> (fast mode: the per-splat accumulator rows), then the activations'
 // backward (activate_bwd_splat) and the SH rest coefficients' backward (sh_grad_row, the rows staged in LDS and copied
-// out contiguously) on the chain's outputs -- the functions gstex_raster_setup_bwd_aabb, gstex_activate_bwd and
+// out contiguously) on the chain's outputs -- the functions gstex_raster_setup_bwd (fold_aabb), gstex_activate_bwd and
 // gstex_sh_rest_bwd run, on the same values: bit-identical gradients, two launches fewer.
 constexpr int kEpiBlock = 256;
 __global__ __launch_bounds__(kEpiBlock) void train_epilogue_kernel(
@@ -1781,64 +1782,51 @@ extern "C" int gstex_raster_setup(int32_t n, const float* means, const float* sc
     return launch_status("gstex_raster_setup");
 }
 
-extern "C" int gstex_raster_fwd(const gstex_camera* cam, int32_t channels, int32_t settings,
-                                const float* background, const float* records, const double* hp_records,
-                                const int32_t* tile_ranges,
-                                const int32_t* tile_order, const int32_t* sorted_ids, const float* texture,
-                                int64_t n_texels, float tex_scale, float tex_bias, float* out_img, float* out_depth, float* out_reg, float* out_alpha, float* out_tex,
-                                float* out_normal, float* state, int64_t n_isect, void* aux, void* stream) {
-    return gstex_raster_fwd_zero(cam, channels, settings, background, records, hp_records, tile_ranges, tile_order,
-                                 sorted_ids,
-                                 texture, n_texels, tex_scale, tex_bias, out_img, out_depth, out_reg, out_alpha,
-                                 out_tex, out_normal, state, n_isect, aux, nullptr, 0, nullptr, 0, stream);
-}
-
-extern "C" int gstex_raster_fwd_zero(const gstex_camera* cam, int32_t channels, int32_t settings,
-                                     const float* background, const float* records, const double* hp_records,
-                                     const int32_t* tile_ranges,
-                                     const int32_t* tile_order, const int32_t* sorted_ids, const float* texture,
-                                     int64_t n_texels, float tex_scale, float tex_bias, float* out_img,
-                                     float* out_depth, float* out_reg, float* out_alpha, float* out_tex,
-                                     float* out_normal, float* state, int64_t n_isect, void* aux, float* zero_buf,
-                                     int64_t zero_floats, float* zero_buf2, int64_t zero_floats2, void* stream) {
-    GSTEX_REQUIRE(zero_floats >= 0 && (zero_floats == 0 || zero_buf) && zero_floats2 >= 0 &&
-                  (zero_floats2 == 0 || zero_buf2), "gstex_raster_fwd: invalid zero_buf / zero_floats");
-    GSTEX_REQUIRE(cam && cam->H > 0 && cam->W > 0, "gstex_raster_fwd: invalid camera");
+extern "C" int gstex_raster_fwd(const gstex_raster_fwd_args* a, void* stream) {
+    GSTEX_REQUIRE(a, "gstex_raster_fwd: null args");
+    GSTEX_REQUIRE(a->zero_floats >= 0 && (a->zero_floats == 0 || a->zero_buf) && a->zero_floats2 >= 0 &&
+                  (a->zero_floats2 == 0 || a->zero_buf2), "gstex_raster_fwd: invalid zero_buf / zero_floats");
+    const gstex_raster_scene& s = a->scene;
+    const gstex_camera* cam = &s.cam;
+    const int channels = s.channels;
+    GSTEX_REQUIRE(cam->H > 0 && cam->W > 0, "gstex_raster_fwd: invalid camera");
     GSTEX_REQUIRE(cam->block == kTile, "gstex_raster_fwd: block_width must be %d (got %d)", kTile, cam->block);
     GSTEX_REQUIRE(channels >= 1 && channels <= 8, "gstex_raster_fwd: channels must be in [1, 8] (got %d)",
                   channels);
-    GSTEX_REQUIRE(n_texels >= 0 && n_texels * channels < (int64_t)INT32_MAX, "gstex_raster_fwd: n_texels out of range");
-    GSTEX_REQUIRE(n_texels == 0 || texture, "gstex_raster_fwd: null texture");
-    int rc = check_settings(settings & ~GSTEX_SETTING_AUX_ZEROED);
+    GSTEX_REQUIRE(s.n_texels >= 0 && s.n_texels * channels < (int64_t)INT32_MAX,
+                  "gstex_raster_fwd: n_texels out of range");
+    GSTEX_REQUIRE(s.n_texels == 0 || s.texture, "gstex_raster_fwd: null texture");
+    int rc = check_settings(s.settings);
     if (rc) return rc;
-    GSTEX_REQUIRE(tile_ranges && out_img && out_alpha && out_tex && state, "gstex_raster_fwd: null pointer");
-    const bool geo = out_depth || out_reg || out_normal;
-    GSTEX_REQUIRE(!geo || (out_depth && out_reg && out_normal),
+    GSTEX_REQUIRE(s.tile_ranges && a->out_img && a->out_alpha && a->out_tex && s.state,
+                  "gstex_raster_fwd: null pointer");
+    const bool geo = a->out_depth || a->out_reg || a->out_normal;
+    GSTEX_REQUIRE(!geo || (a->out_depth && a->out_reg && a->out_normal),
                   "gstex_raster_fwd: out_depth, out_reg and out_normal must be all given or all NULL");
-    GSTEX_REQUIRE(n_isect >= 0 && n_isect < (int64_t)INT32_MAX, "gstex_raster_fwd: n_isect out of range");
+    GSTEX_REQUIRE(s.n_isect >= 0 && s.n_isect < (int64_t)INT32_MAX, "gstex_raster_fwd: n_isect out of range");
     const int tiles_x = (cam->W + kTile - 1) / kTile, tiles_y = (cam->H + kTile - 1) / kTile;
     CamArgs dc = to_device_camera(*cam);
     hipStream_t st = as_stream(stream);
     const int nblk = tiles_x * tiles_y;
-    const AuxLayout al = aux_layout(n_isect, nblk, channels);
-    const AuxPtrs ap = aux_ptrs(aux, al);
+    const AuxLayout al = aux_layout(s.n_isect, nblk, channels);
+    const AuxPtrs ap = aux_ptrs(s.aux, al);
     // one fill: unit costs (units the forward never reaches keep 0; the backward skips them), the launch order
     // (0 = no unit at that position) and the unit-order histogram the forward builds (contiguous in the layout)
-    if (aux && !(settings & GSTEX_SETTING_AUX_ZEROED) &&
+    if (s.aux && !a->aux_zeroed &&
         hipMemsetAsync(ap.cost, 0, al.order_ws - al.cost + (size_t)2 * kUnitBins * 4, st) != hipSuccess)
         return launch_status("gstex_raster_fwd (aux)");
-    settings &= ~GSTEX_SETTING_AUX_ZEROED;
     ZeroBufs zbuf;
-    zbuf.p[0] = zero_floats > 0 ? zero_buf : nullptr;
-    zbuf.n[0] = zero_floats;
-    zbuf.p[1] = zero_floats2 > 0 ? zero_buf2 : nullptr;
-    zbuf.n[1] = zero_floats2;
+    zbuf.p[0] = a->zero_floats > 0 ? a->zero_buf : nullptr;
+    zbuf.n[0] = a->zero_floats;
+    zbuf.p[1] = a->zero_floats2 > 0 ? a->zero_buf2 : nullptr;
+    zbuf.n[1] = a->zero_floats2;
     int fgrid = fwd_grid(tiles_x, tiles_y);
 #define GSTEX_FWD(CC, GG)                                                                                      \
     raster_fwd_kernel<CC, GG><<<fgrid, kThreads, 0, st>>>(                                                    \
-        dc, tiles_x, settings, background, channels, (const float4*)records, hp_records,                      \
-        (const int2*)tile_ranges, tile_order, sorted_ids, texture, (int)n_texels, tex_scale, tex_bias, out_img, out_depth, out_reg,     \
-        out_alpha, out_tex, out_normal, (float4*)state, ap, nblk, zbuf)
+        dc, tiles_x, s.settings, s.background, channels, (const float4*)s.records, s.hp_records,              \
+        (const int2*)s.tile_ranges, a->tile_order, s.sorted_ids, s.texture, (int)s.n_texels, s.tex_scale,     \
+        s.tex_bias, a->out_img, a->out_depth, a->out_reg, a->out_alpha, a->out_tex, a->out_normal,            \
+        (float4*)s.state, ap, nblk, zbuf)
     if (channels == 3 && geo) GSTEX_FWD(3, true);
     else if (channels == 3) GSTEX_FWD(3, false);
     else if (channels == 6 && geo) GSTEX_FWD(6, true);
@@ -1849,43 +1837,49 @@ extern "C" int gstex_raster_fwd_zero(const gstex_camera* cam, int32_t channels, 
     return launch_status("gstex_raster_fwd");
 }
 
-namespace {
-int raster_bwd_impl(const gstex_camera* cam, int32_t channels, int32_t settings, const float* background,
-                    const float* records, const double* hp_records, const int32_t* tile_ranges, const int32_t* sorted_ids,
-                    const int32_t* sorted_slots, const float* texture, int64_t n_texels, float tex_scale,
-                    float tex_bias, const float* state, const float* v_img, const float* v_depth, const float* v_reg,
-                    const float* v_alpha, const float* v_tex, const float* v_normal, int64_t n_isect, float* partials,
-                    uint32_t* row_flags, float* v_texture, void* aux, ZeroBufs zbuf, void* stream) {
-    GSTEX_REQUIRE(cam && cam->H > 0 && cam->W > 0, "gstex_raster_bwd: invalid camera");
+extern "C" int gstex_raster_bwd(const gstex_raster_bwd_args* a, void* stream) {
+    GSTEX_REQUIRE(a, "gstex_raster_bwd: null args");
+    GSTEX_REQUIRE(a->zero_floats >= 0 && (a->zero_floats == 0 || a->zero_buf) &&
+                      (!a->zero_buf || a->zero_buf != a->v_texture),
+                  "gstex_raster_bwd: invalid zero_buf / zero_floats (it must not be the gradient accumulated)");
+    const gstex_raster_scene& s = a->scene;
+    const gstex_camera* cam = &s.cam;
+    const int channels = s.channels;
+    const int settings = s.settings;
+    GSTEX_REQUIRE(cam->H > 0 && cam->W > 0, "gstex_raster_bwd: invalid camera");
     GSTEX_REQUIRE(cam->block == kTile, "gstex_raster_bwd: block_width must be %d", kTile);
     GSTEX_REQUIRE(channels >= 1 && channels <= 8, "gstex_raster_bwd: channels must be in [1, 8]");
     int rc = check_settings(settings);
     if (rc) return rc;
-    GSTEX_REQUIRE(tile_ranges && state && aux, "gstex_raster_bwd: null pointer (tile_ranges, state and the forward's aux)");
-    GSTEX_REQUIRE(n_isect >= 0 && n_isect < (int64_t)INT32_MAX, "gstex_raster_bwd: n_isect out of range");
-    GSTEX_REQUIRE(n_isect == 0 || (partials && sorted_ids && sorted_slots), "gstex_raster_bwd: null pair buffer");
-    GSTEX_REQUIRE(n_texels >= 0 && n_texels * channels < (int64_t)INT32_MAX, "gstex_raster_bwd: n_texels out of range");
-    GSTEX_REQUIRE(n_texels == 0 || (texture && v_texture), "gstex_raster_bwd: null texture");
-    GSTEX_REQUIRE(!(settings & GSTEX_SETTING_EVAL_NORMAL) || !v_normal,
+    GSTEX_REQUIRE(s.tile_ranges && s.state && s.aux,
+                  "gstex_raster_bwd: null pointer (tile_ranges, state and the forward's aux)");
+    GSTEX_REQUIRE(s.n_isect >= 0 && s.n_isect < (int64_t)INT32_MAX, "gstex_raster_bwd: n_isect out of range");
+    GSTEX_REQUIRE(s.n_isect == 0 || (a->partials && s.sorted_ids && a->sorted_slots),
+                  "gstex_raster_bwd: null pair buffer");
+    GSTEX_REQUIRE(s.n_texels >= 0 && s.n_texels * channels < (int64_t)INT32_MAX,
+                  "gstex_raster_bwd: n_texels out of range");
+    GSTEX_REQUIRE(s.n_texels == 0 || (s.texture && a->v_texture), "gstex_raster_bwd: null texture");
+    GSTEX_REQUIRE(!(settings & GSTEX_SETTING_EVAL_NORMAL) || !a->v_normal,
                   "gstex_raster_bwd: settings bit 15 (unit-normal eval render) has no normal gradient; pass v_normal = NULL");
     const int tiles_x = (cam->W + kTile - 1) / kTile, tiles_y = (cam->H + kTile - 1) / kTile;
     CamArgs dc = to_device_camera(*cam);
     hipStream_t st = as_stream(stream);
-    const AuxLayout al = aux_layout(n_isect, tiles_x * tiles_y, channels);
-    const AuxPtrs ap = aux_ptrs(aux, al);
-    if (n_isect > 0 && row_flags && hipMemsetAsync(row_flags, 0, (size_t)n_isect * 4, st) != hipSuccess)
+    const AuxLayout al = aux_layout(s.n_isect, tiles_x * tiles_y, channels);
+    const AuxPtrs ap = aux_ptrs(s.aux, al);
+    if (s.n_isect > 0 && a->row_flags && hipMemsetAsync(a->row_flags, 0, (size_t)s.n_isect * 4, st) != hipSuccess)
         return launch_status("gstex_raster_bwd (row_flags)");
     // costliest units first, from the histogram the forward built (order entries are unit + 1)
     rc = unit_order_from_hist((int32_t)al.n_units, ap.cost, ap.order, ap.order_ws, st);
     if (rc) return rc;
     // depth / distortion / normal gradients present?  (the distortion one only counts when enabled)
-    const bool geo = v_depth || v_normal || (v_reg && (settings & GSTEX_SETTING_DIST_REG));
+    const bool geo = a->v_depth || a->v_normal || (a->v_reg && (settings & GSTEX_SETTING_DIST_REG));
+    const ZeroBufs zbuf{{a->zero_floats > 0 ? a->zero_buf : nullptr, nullptr}, {a->zero_floats, 0}};
 #define GSTEX_BWD(CC, GG)                                                                                      \
     raster_bwd_kernel<CC, GG><<<(unsigned)al.n_units, 64, 0, st>>>(                                            \
-        dc, tiles_x, settings, background, channels, (const float4*)records, hp_records,                      \
-        (const int2*)tile_ranges, sorted_ids, sorted_slots, texture, (int)n_texels, tex_scale, tex_bias, (const float4*)state,           \
-        v_img, v_depth, v_reg, v_alpha, v_tex, v_normal, partials, (unsigned char*)row_flags, v_texture, ap,   \
-        zbuf)
+        dc, tiles_x, settings, s.background, channels, (const float4*)s.records, s.hp_records,                \
+        (const int2*)s.tile_ranges, s.sorted_ids, a->sorted_slots, s.texture, (int)s.n_texels, s.tex_scale,   \
+        s.tex_bias, (const float4*)s.state, a->v_img, a->v_depth, a->v_reg, a->v_alpha, a->v_tex, a->v_normal, \
+        a->partials, (unsigned char*)a->row_flags, a->v_texture, ap, zbuf)
     if (channels == 3 && !geo) GSTEX_BWD(3, false);
     else if (channels == 3) GSTEX_BWD(3, true);
     else if (channels == 6 && !geo) GSTEX_BWD(6, false);
@@ -1895,78 +1889,36 @@ int raster_bwd_impl(const gstex_camera* cam, int32_t channels, int32_t settings,
 #undef GSTEX_BWD
     return launch_status("gstex_raster_bwd");
 }
-}  // namespace
-
-extern "C" int gstex_raster_bwd(const gstex_camera* cam, int32_t channels, int32_t settings,
-                                const float* background, const float* records, const double* hp_records,
-                                const int32_t* tile_ranges,
-                                const int32_t* sorted_ids, const int32_t* sorted_slots,
-                                const float* texture, int64_t n_texels, float tex_scale, float tex_bias,
-                                const float* state, const float* v_img,
-                                const float* v_depth, const float* v_reg, const float* v_alpha, const float* v_tex,
-                                const float* v_normal, int64_t n_isect, float* partials, uint32_t* row_flags,
-                                float* v_texture, void* aux, void* stream) {
-    return raster_bwd_impl(cam, channels, settings, background, records, hp_records, tile_ranges, sorted_ids, sorted_slots,
-                           texture, n_texels, tex_scale, tex_bias, state, v_img, v_depth, v_reg, v_alpha, v_tex,
-                           v_normal, n_isect, partials, row_flags, v_texture, aux, ZeroBufs{{nullptr, nullptr}, {0, 0}},
-                           stream);
-}
-
-extern "C" int gstex_raster_bwd_zero(const gstex_camera* cam, int32_t channels, int32_t settings,
-                                     const float* background, const float* records, const double* hp_records,
-                                     const int32_t* tile_ranges,
-                                     const int32_t* sorted_ids, const int32_t* sorted_slots,
-                                     const float* texture, int64_t n_texels, float tex_scale, float tex_bias,
-                                     const float* state, const float* v_img,
-                                     const float* v_depth, const float* v_reg, const float* v_alpha,
-                                     const float* v_tex, const float* v_normal, int64_t n_isect, float* partials,
-                                     uint32_t* row_flags, float* v_texture, void* aux, float* zero_buf,
-                                     int64_t zero_floats, void* stream) {
-    GSTEX_REQUIRE(zero_floats >= 0 && (zero_floats == 0 || zero_buf) && zero_buf != v_texture,
-                  "gstex_raster_bwd_zero: invalid zero_buf / zero_floats (it must not be the gradient accumulated)");
-    return raster_bwd_impl(cam, channels, settings, background, records, hp_records, tile_ranges, sorted_ids, sorted_slots,
-                           texture, n_texels, tex_scale, tex_bias, state, v_img, v_depth, v_reg, v_alpha, v_tex,
-                           v_normal, n_isect, partials, row_flags, v_texture, aux,
-                           ZeroBufs{{zero_floats > 0 ? zero_buf : nullptr, nullptr}, {zero_floats, 0}}, stream);
-}
 
 extern "C" size_t gstex_raster_aux_bytes(int64_t n_isect, int32_t n_tiles, int32_t channels) {
     if (n_isect < 0 || n_tiles < 0 || channels < 1 || channels > 8) return 0;
     return aux_layout(n_isect, n_tiles, channels).bytes;
 }
 
-template <bool FOLD_AABB>
-int setup_bwd_launch(int32_t n, const float* means, const float* scales, float glob_scale, const float* quats,
-                     const float* umap, const float* vmap, const int32_t* nth, const int32_t* offsets,
-                     float* partials, const uint32_t* row_flags, int32_t rs, int64_t n_rows, const gstex_camera* cam,
-                     float* v_means, float* v_scales, float* v_quats, float* v_rgbs, float* v_opacities,
-                     float* v_centers, float* v_uv0, hipStream_t st) {
+extern "C" int gstex_raster_setup_bwd(const gstex_raster_setup_bwd_args* a, void* stream) {
+    GSTEX_REQUIRE(a && a->n >= 0, "gstex_raster_setup_bwd: invalid arguments");
+    if (a->n == 0) return GSTEX_OK;
+    GSTEX_REQUIRE(a->means && a->scales && a->quats && a->umap && a->vmap && a->num_tiles_hit && a->offsets &&
+                      a->partials && a->v_means && a->v_scales && a->v_quats && a->v_rgbs && a->v_opacities &&
+                      a->v_centers && a->v_uv0,
+                  "gstex_raster_setup_bwd: null pointer");
+    GSTEX_REQUIRE(a->row_floats == kPartRow || a->row_floats == kPartRowGeo,
+                  "gstex_raster_setup_bwd: row_floats must be %d or %d (got %d)", kPartRow, kPartRowGeo, a->row_floats);
+    hipStream_t st = as_stream(stream);
     // no row_flags: the backward accumulated per splat (atomic mode), nothing to sum
-    if (row_flags)
-        setup_bwd_sum_kernel<<<div_up(n, kSetupBwdRows), 256, 0, st>>>(n, nth, offsets, partials, row_flags, rs, n_rows);
-    setup_bwd_chain_kernel<FOLD_AABB><<<div_up(n, 256), 256, 0, st>>>(
-        n, means, scales, glob_scale, quats, umap, vmap, nth, offsets, partials, rs, row_flags == nullptr, n_rows,
-        to_device_camera(*cam), v_means, v_scales, v_quats, v_rgbs, v_opacities, v_centers, v_uv0);
-    return GSTEX_OK;
-}
-
-template <bool FOLD_AABB>
-int setup_bwd_entry(const char* name, int32_t n, const float* means, const float* scales, float glob_scale,
-                    const float* quats, const float* umap, const float* vmap, const int32_t* num_tiles_hit,
-                    const int32_t* offsets, float* partials, const uint32_t* row_flags, int32_t row_floats,
-                    int64_t n_rows, const gstex_camera* cam, float* v_means, float* v_scales, float* v_quats,
-                    float* v_rgbs, float* v_opacities, float* v_centers, float* v_uv0, void* stream) {
-    GSTEX_REQUIRE(n >= 0 && cam, "%s: invalid arguments", name);
-    if (n == 0) return GSTEX_OK;
-    GSTEX_REQUIRE(means && scales && quats && umap && vmap && num_tiles_hit && offsets && partials && v_means &&
-                      v_scales && v_quats && v_rgbs && v_opacities && v_centers && v_uv0,
-                  "%s: null pointer", name);
-    GSTEX_REQUIRE(row_floats == kPartRow || row_floats == kPartRowGeo, "%s: row_floats must be %d or %d (got %d)",
-                  name, kPartRow, kPartRowGeo, row_floats);
-    setup_bwd_launch<FOLD_AABB>(n, means, scales, glob_scale, quats, umap, vmap, num_tiles_hit, offsets, partials,
-                                row_flags, row_floats, n_rows, cam, v_means, v_scales, v_quats, v_rgbs, v_opacities,
-                                v_centers, v_uv0, as_stream(stream));
-    return launch_status(name);
+    if (a->row_flags)
+        setup_bwd_sum_kernel<<<div_up(a->n, kSetupBwdRows), 256, 0, st>>>(a->n, a->num_tiles_hit, a->offsets,
+                                                                           a->partials, a->row_flags, a->row_floats,
+                                                                           a->n_rows);
+#define GSTEX_CHAIN(FOLD)                                                                                      \
+    setup_bwd_chain_kernel<FOLD><<<div_up(a->n, 256), 256, 0, st>>>(                                          \
+        a->n, a->means, a->scales, a->glob_scale, a->quats, a->umap, a->vmap, a->num_tiles_hit, a->offsets,   \
+        a->partials, a->row_floats, a->row_flags == nullptr, a->n_rows, to_device_camera(a->cam), a->v_means, \
+        a->v_scales, a->v_quats, a->v_rgbs, a->v_opacities, a->v_centers, a->v_uv0)
+    if (!a->fold_aabb) GSTEX_CHAIN(false);
+    else GSTEX_CHAIN(true);
+#undef GSTEX_CHAIN
+    return launch_status("gstex_raster_setup_bwd");
 }
 
 extern "C" int gstex_train_epilogue(const gstex_train_epilogue_args* a, void* stream) {
@@ -1976,10 +1928,29 @@ extern "C" int gstex_train_epilogue(const gstex_train_epilogue_args* a, void* st
                        (size_t)kEpiBlock * a->n_rest * 3 * sizeof(float) <= 65536 &&
                        a->n_rest >= (a->sh_degree + 1) * (a->sh_degree + 1) - 1;
     if (!fused) {  // the per-op entry points (an SH layout whose rows do not fit the staging)
-        int rc = gstex_raster_setup_bwd_aabb(a->n, a->means, a->scales, 1.0f, a->quats_n, a->opacities, a->umap,
-                                             a->vmap, a->num_tiles_hit, a->offsets, a->partials, nullptr, kPartRow,
-                                             -1, &a->cam, a->v_means, a->v_scales_act, a->v_quats_n, a->v_rgbs,
-                                             a->v_opacities_act, a->v_centers, a->v_uv0, stream);
+        gstex_raster_setup_bwd_args sb{};
+        sb.n = a->n;
+        sb.glob_scale = 1.0f;
+        sb.row_floats = kPartRow;
+        sb.fold_aabb = 1;
+        sb.n_rows = -1;
+        sb.cam = a->cam;
+        sb.means = a->means;
+        sb.scales = a->scales;
+        sb.quats = a->quats_n;
+        sb.umap = a->umap;
+        sb.vmap = a->vmap;
+        sb.num_tiles_hit = a->num_tiles_hit;
+        sb.offsets = a->offsets;
+        sb.partials = a->partials;
+        sb.v_means = a->v_means;
+        sb.v_scales = a->v_scales_act;
+        sb.v_quats = a->v_quats_n;
+        sb.v_rgbs = a->v_rgbs;
+        sb.v_opacities = a->v_opacities_act;
+        sb.v_centers = a->v_centers;
+        sb.v_uv0 = a->v_uv0;
+        int rc = gstex_raster_setup_bwd(&sb, stream);
         if (rc) return rc;
         rc = gstex_sh_rest_bwd(a->n, a->sh_degree, a->n_rest, a->viewdirs, a->v_rgbs, a->v_features_rest, stream);
         if (rc) return rc;
@@ -2002,31 +1973,6 @@ extern "C" int gstex_train_epilogue(const gstex_train_epilogue_args* a, void* st
         a->v_quats, a->v_log_scales, a->v_opac_logits, a->v_features_rest, a->v_scales_act, a->v_quats_n, a->v_rgbs,
         a->v_opacities_act, a->v_centers, a->v_uv0);
     return launch_status("gstex_train_epilogue");
-}
-
-extern "C" int gstex_raster_setup_bwd(int32_t n, const float* means, const float* scales, float glob_scale,
-                                      const float* quats, const float* opacities, const float* umap,
-                                      const float* vmap, const int32_t* num_tiles_hit, const int32_t* offsets,
-                                      float* partials, const uint32_t* row_flags, int32_t row_floats, int64_t n_rows,
-                                      const gstex_camera* cam, float* v_means, float* v_scales, float* v_quats,
-                                      float* v_rgbs, float* v_opacities, float* v_centers, float* v_uv0, void* stream) {
-    (void)opacities;
-    return setup_bwd_entry<false>("gstex_raster_setup_bwd", n, means, scales, glob_scale, quats, umap, vmap,
-                                  num_tiles_hit, offsets, partials, row_flags, row_floats, n_rows, cam, v_means,
-                                  v_scales, v_quats, v_rgbs, v_opacities, v_centers, v_uv0, stream);
-}
-
-extern "C" int gstex_raster_setup_bwd_aabb(int32_t n, const float* means, const float* scales, float glob_scale,
-                                           const float* quats, const float* opacities, const float* umap,
-                                           const float* vmap, const int32_t* num_tiles_hit, const int32_t* offsets,
-                                           float* partials, const uint32_t* row_flags, int32_t row_floats,
-                                           int64_t n_rows, const gstex_camera* cam, float* v_means, float* v_scales,
-                                           float* v_quats, float* v_rgbs, float* v_opacities, float* v_centers,
-                                           float* v_uv0, void* stream) {
-    (void)opacities;
-    return setup_bwd_entry<true>("gstex_raster_setup_bwd_aabb", n, means, scales, glob_scale, quats, umap, vmap,
-                                 num_tiles_hit, offsets, partials, row_flags, row_floats, n_rows, cam, v_means,
-                                 v_scales, v_quats, v_rgbs, v_opacities, v_centers, v_uv0, stream);
 }
 
 extern "C" int gstex_texture_edit(const gstex_camera* cam, int32_t settings, const float* records,

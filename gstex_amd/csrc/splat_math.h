@@ -299,7 +299,7 @@ __device__ __forceinline__ int block_excl_scan(int v, int* s_wave, int* total) {
     return wave_off + incl - v;
 }
 
-// Pair-capacity guard (gstex_scan_offsets_guarded, ABI 13), applied by the thread that writes the total out[n]: the
+// Pair-capacity guard (gstex_scan_offsets with a guard, ABI 13), applied by the thread that writes the total out[n]: the
 // step's overflow flag (1.0f when the total exceeds the pair buffers' capacity; the first render of a step writes it,
 // later ones OR into it) and, when given, the total in device-writable host memory (no copy, no synchronisation:
 // the host polls the word, which it set to a sentinel before the launch).  Plain vector stores.

@@ -11,7 +11,7 @@
 //                       sums before it (kBlocksPerTile = 4 per tile; at most n / 256 L2-resident words), then scans its tile as
 //                       binning.hip's scan_final_kernel does (same integers, same guard);
 //                       its grid also zeroes the binning's tile counters and the raster forward's accumulated aux span
-//                       (args.raster_aux), so neither needs its fill launch (GSTEX_SETTING_AUX_ZEROED);
+//                       (args.raster_aux), so neither needs its fill launch (gstex_raster_fwd_args.aux_zeroed);
 // then the capped binning.  Seven launches fewer and no host time between the launches (the device waits through that
 // whenever a step starts on an idle device, after a synchronisation).
 #include "gstex_common.h"
@@ -195,9 +195,9 @@ extern "C" int gstex_train_prologue(const gstex_train_prologue_args* a, void* st
         if (rc) return rc;
         rc = gstex_sh_rest_fwd(a->n, a->sh_degree, a->n_rest, a->viewdirs, a->features_rest, a->rgbs, stream);
         if (rc) return rc;
-        rc = gstex_scan_offsets_guarded(a->n, a->num_tiles_hit, a->offsets, a->scan_workspace,
-                                        a->scan_workspace_bytes, &a->guard, stream);
-        if (rc == 0 && a->raster_aux) {  // (the caller passes GSTEX_SETTING_AUX_ZEROED to the forward)
+        rc = gstex_scan_offsets(a->n, a->num_tiles_hit, a->offsets, a->scan_workspace, a->scan_workspace_bytes,
+                                &a->guard, stream);
+        if (rc == 0 && a->raster_aux) {  // (the caller sets aux_zeroed in the forward's args)
             const int tx = (pre.W + pre.block - 1) / pre.block, ty = (pre.H + pre.block - 1) / pre.block;
             const ZeroSpan za = raster_aux_zero_span(a->raster_aux, a->capacity, tx * ty, a->raster_channels);
             if (hipMemsetAsync(za.ptr, 0, za.bytes, as_stream(stream)) != hipSuccess)
@@ -211,11 +211,9 @@ extern "C" int gstex_train_prologue(const gstex_train_prologue_args* a, void* st
                                 a->hp_records, stream);
         if (rc) return rc;
     }
-    if (fused)  // the tile counters were zeroed by train_scan_kernel
-        return bin_sort_capped_prezeroed(a->n, a->capacity, a->centers, a->extents, a->depths, a->offsets, a->cam.H,
-                                         a->cam.W, a->cam.block, a->tile_ranges, a->sorted_ids, a->sorted_slots,
-                                         a->tile_order, a->bin_workspace, a->bin_workspace_bytes, stream);
-    return gstex_bin_sort_capped(a->n, a->capacity, a->centers, a->extents, a->depths, a->num_tiles_hit, a->offsets,
-                                 a->cam.H, a->cam.W, a->cam.block, a->tile_ranges, a->sorted_ids, a->sorted_slots,
-                                 a->tile_order, a->bin_workspace, a->bin_workspace_bytes, stream);
+    // (fused: the tile counters were zeroed by train_scan_kernel)
+    return gstex_bin_sort(a->n, a->capacity, a->centers, a->extents, a->depths, a->offsets, a->cam.H, a->cam.W,
+                          a->cam.block, a->tile_ranges, a->sorted_ids, a->sorted_slots, a->tile_order,
+                          GSTEX_BIN_CAPPED | (fused ? GSTEX_BIN_COUNT_ZEROED : 0), a->bin_workspace,
+                          a->bin_workspace_bytes, stream);
 }

@@ -185,7 +185,7 @@ class GradSync:
         if self.rebuild():
             return  # a new buffer is zero
         if getattr(self.trainer, "texture_grad_zeroed_by_update", False):
-            # the texel slice is zeroed by the next differentiable raster forward (gstex_raster_fwd_zero); filling it
+            # the texel slice is zeroed by the next differentiable raster forward (gstex_raster_fwd zero_buf); filling it
             # here would pre-empt the deferred texel update (defer_texture) still reading it
             self.flat[self._z0:self._tail_off].zero_()
         else:

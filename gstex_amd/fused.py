@@ -121,18 +121,21 @@ class _TrainRender(torch.autograd.Function):
         if texture_ready is not None:  # the deferred texel update waiting for its collective: the raster forward
             texture_ready()            # is the first reader of the texels
         texture = tr.texture_dc
-        zn = sink.numel() if zero_sink else 0
-        aux_zeroed = _lib.SETTING_AUX_ZEROED if sizes["aux"] else 0  # (zeroed by the prologue's scan kernel)
-        ops._launch("gstex_raster_fwd_zero", cam, C, int(tr.settings) | aux_zeroed, ptr(tr._bg_zero), P["records"],
-                    P["hp"] if ops.HP_RECORDS else None, P["tile_ranges"], P["tile_order"], P["sorted_ids"], ptr(texture), texture.shape[0],
-                    SH_C0, 0.5, P["img"], None, None, P["alpha"], P["tex"], None, P["state"], cap,
-                    P["aux"] if sizes["aux"] else None, ptr(sink) if zero_sink else None, zn, P["partials"],
-                    PARTIAL_FLOATS * n, st)
+        scene = _lib.GstexRasterScene(
+            cam=cam, channels=C, settings=int(tr.settings), background=ptr(tr._bg_zero), records=P["records"],
+            hp_records=P["hp"] if ops.HP_RECORDS else None, tile_ranges=P["tile_ranges"], sorted_ids=P["sorted_ids"],
+            texture=ptr(texture), n_texels=texture.shape[0], tex_scale=SH_C0, tex_bias=0.5, state=P["state"],
+            n_isect=cap, aux=P["aux"] if sizes["aux"] else None)
+        fwd = _lib.GstexRasterFwdArgs(
+            scene=scene, tile_order=P["tile_order"], out_img=P["img"], out_alpha=P["alpha"], out_tex=P["tex"],
+            zero_buf=ptr(sink) if zero_sink else None, zero_floats=sink.numel() if zero_sink else 0,
+            zero_buf2=P["partials"], zero_floats2=PARTIAL_FLOATS * n,
+            aux_zeroed=1 if sizes["aux"] else 0)  # (zeroed by the prologue's scan kernel)
+        ops._launch("gstex_raster_fwd", ctypes.byref(fwd), st)
         ctx.tr, ctx.arena, ctx.P, ctx.cam_keep = tr, arena, P, (vm, cw)
-        ctx.cam, ctx.cap, ctx.sink, ctx.degree, ctx.goff, ctx.gfloats = cam, cap, sink, int(degree), goff, gfloats
+        ctx.scene, ctx.sink, ctx.degree, ctx.goff, ctx.gfloats = scene, sink, int(degree), goff, gfloats
         ctx.on_grad = on_grad
         ctx.zero_next = zero_next
-        ctx.has_aux = sizes["aux"] > 0
         ctx.save_for_backward(quats, log_scales)
         ctx.set_materialize_grads(False)
         img = _view(arena, off["img"], (H, W, 3))
@@ -143,24 +146,21 @@ class _TrainRender(torch.autograd.Function):
     @staticmethod
     def backward(ctx, v_img, v_alpha, v_tex):
         quats, log_scales = ctx.saved_tensors
-        tr, P, cam = ctx.tr, ctx.P, ctx.cam
+        tr, P, scene = ctx.tr, ctx.P, ctx.scene
         n = quats.shape[0]
         dev = quats.device
         st = _lib.stream_of(dev)
         c = lambda t: None if t is None else t.contiguous()  # noqa: E731
         v_img, v_alpha, v_tex = c(v_img), c(v_alpha), c(v_tex)
-        texture = tr.texture_dc
-        bwd_args = (cam, 3, int(tr.settings), ptr(tr._bg_zero),
-                    P["records"], P["hp"] if ops.HP_RECORDS else None, P["tile_ranges"], P["sorted_ids"], P["sorted_slots"], ptr(texture),
-                    texture.shape[0], SH_C0, 0.5, P["state"], ptr(v_img), None, None, ptr(v_alpha), ptr(v_tex), None,
-                    ctx.cap, P["partials"], None, ptr(ctx.sink), P["aux"] if ctx.has_aux else None)
+        bwd = _lib.GstexRasterBwdArgs(
+            scene=scene, sorted_slots=P["sorted_slots"], v_img=ptr(v_img), v_alpha=ptr(v_alpha), v_tex=ptr(v_tex),
+            partials=P["partials"], v_texture=ptr(ctx.sink))
         zn = ctx.zero_next
         if zn is not None and zn is tr._tex_grad_next and zn.data_ptr() != ctx.sink.data_ptr():
             # the trainer's other texel-gradient buffer, zeroed by this backward's grid for the next step
-            ops._launch("gstex_raster_bwd_zero", *bwd_args, ptr(zn), zn.numel(), st)
+            bwd.zero_buf, bwd.zero_floats = ptr(zn), zn.numel()
             tr._next_zeroed = True
-        else:
-            ops._launch("gstex_raster_bwd", *bwd_args, st)
+        ops._launch("gstex_raster_bwd", ctypes.byref(bwd), st)
         ctx.zero_next = None
         if ctx.on_grad is not None:
             ctx.on_grad()  # the texel gradient is complete in stream order (GradSync starts its tail collective)
@@ -170,7 +170,7 @@ class _TrainRender(torch.autograd.Function):
         n_rest = tr.features_rest.shape[1]
         # setup bwd -> activations bwd + SH rest bwd in one launch (gstex_train_epilogue)
         e = _lib.GstexTrainEpilogueArgs(
-            n=n, sh_degree=ctx.degree, n_rest=n_rest, cam=cam, means=ptr(means), scales=P["scales"],
+            n=n, sh_degree=ctx.degree, n_rest=n_rest, cam=scene.cam, means=ptr(means), scales=P["scales"],
             quats_n=P["quats_n"], quats=ptr(quats), log_scales=ptr(log_scales), opacities=P["opacities"],
             umap=P["umap"], vmap=P["vmap"], viewdirs=P["viewdirs"], num_tiles_hit=P["num_tiles_hit"],
             offsets=P["offsets"], partials=P["partials"], v_means=g["means"], v_quats=g["quats"],

@@ -173,7 +173,7 @@ class GStexTrainer:
         self._pending_tex = None
         self._pending_collective = False  # the pending update first waits for a GradSync collective
         # the texel-gradient sink is zeroed by the first differentiable raster forward after an optimizer step
-        # (gstex_raster_fwd_zero), so several renders of one step still accumulate their texel gradients
+        # (gstex_raster_fwd zero_buf), so several renders of one step still accumulate their texel gradients
         self._sink_fresh = True
         # pair_capacity (not in the reference; fused Adam on a HIP device): the training renders size their pair
         # buffers from an ops.PairCapacity instead of reading the pair total back to the host (gstex.py:1045-1052,
@@ -202,7 +202,7 @@ class GStexTrainer:
     def _own_texture_grad(self):
         # the persistent texel-gradient buffer (replaced by a flat-buffer slice when GradSync takes over).  With the
         # fused render a second one: step k's raster backward accumulates into one and zeroes the other
-        # (gstex_raster_bwd_zero), which step k + 1 accumulates into, so no forward spends its grid zeroing 120 MB
+        # (gstex_raster_bwd zero_buf), which step k + 1 accumulates into, so no forward spends its grid zeroing 120 MB
         self._tex_grad = torch.zeros_like(self.texture_dc)
         # (not under GradSync, whose flat-buffer slice is the sink: the second buffer would never be used)
         self._tex_grad_next = (torch.zeros_like(self.texture_dc)
@@ -228,14 +228,14 @@ class GStexTrainer:
     @property
     def texture_grad_zeroed_by_update(self) -> bool:
         """The texel gradient buffer handed to the raster (texture_grad_sink) is zeroed by the raster forward
-        (gstex_raster_fwd_zero) before the backward accumulates into it: a gradient-buffer owner
+        (gstex_raster_fwd zero_buf) before the backward accumulates into it: a gradient-buffer owner
         (gstex_amd.dist.GradSync) must not fill that slice itself (with the deferred texel update, defer_texture, that
         fill would also pre-empt the update still reading it)."""
         return True
 
     def reset_texture_grad(self):
         """Zero the texel-gradient sink lazily: the next differentiable render's raster forward zeroes it before its
-        backward accumulates (gstex_raster_fwd_zero).  Called by zero_grad() and by gstex_amd.dist.GradSync.zero(), so
+        backward accumulates (gstex_raster_fwd zero_buf).  Called by zero_grad() and by gstex_amd.dist.GradSync.zero(), so
         a gradient left by a backward whose step was skipped never leaks into the next step."""
         self._sink_fresh = True
 

@@ -19,7 +19,7 @@ from ._lib import PARTIAL_FLOATS, PARTIAL_FLOATS_PHOTO, REC_FLOATS, call, ptr
 
 BLOCK_WIDTH = 16
 # near-edge-on splats' homogeneous points evaluated from their fp64 setup rows by the raster forward and backward alike
-# (gstex_raster_setup / _fwd_zero / _bwd hp_records, ABI 18); GSTEX_HP=0 evaluates every pair from the
+# (gstex_raster_setup / _fwd / _bwd hp_records, ABI 18); GSTEX_HP=0 evaluates every pair from the
 # fp32 record (the round-5 numerics)
 HP_RECORDS = os.environ.get("GSTEX_HP", "1") != "0"
 # diagnostics: called with (partials, row_flags, records, hp rows) after each raster backward (tools/hp_partials.py)
@@ -57,9 +57,7 @@ def _TIMING_EVENTS(name: str) -> list:
 
 
 def _launch(name: str, *args) -> None:
-    # gstex_raster_fwd_zero times as the forward
-    key = name[:-len("_zero")] if name.endswith("_zero") else name
-    if _TIMING is None or key not in _TIMED or torch.cuda.is_current_stream_capturing():
+    if _TIMING is None or name not in _TIMED or torch.cuda.is_current_stream_capturing():
         call(name, *args)
         return
     # fence-free timing events (_lib.TimingEvent): a default event pair around each launch cost ~10 us of device time
@@ -68,7 +66,7 @@ def _launch(name: str, *args) -> None:
     a.record()
     call(name, *args)
     b.record()
-    _TIMING.setdefault(key, []).append((a, b))
+    _TIMING.setdefault(name, []).append((a, b))
 
 
 # ----------------------------------------------------------------------------------------
@@ -296,46 +294,51 @@ def bin_begin(num_tiles_hit):
     nth = _i32(num_tiles_hit, "num_tiles_hit", (n,))
     offsets = torch.empty((n + 1,), device=dev, dtype=torch.int32)
     ws = torch.empty((max(int(_lib.load().gstex_scan_workspace_size(n)), 1),), device=dev, dtype=torch.uint8)
-    call("gstex_scan_offsets", n, ptr(nth), ptr(offsets), ptr(ws), ws.numel(), _stream(nth))
+    call("gstex_scan_offsets", n, ptr(nth), ptr(offsets), ptr(ws), ws.numel(), None, _stream(nth))
     pending = _start_count(offsets[n]) if offsets.is_cuda else int(offsets[n].item())
     return nth, offsets, pending
 
 
-def bin_finish(begun, centers, extents, depths, H: int, W: int, block_width: int = BLOCK_WIDTH,
-               with_order: bool = False):
-    """Second half of bin_and_sort: wait for the pair count, size the pair buffers, bin and sort.  with_order:
-    also return the largest-first tile order the sort ranked (gstex_bin_sort_ordered; == tile_order(ranges))."""
-    nth, offsets, pending = begun
+def _bin_sort(nth, offsets, n_isect: int, centers, extents, depths, H: int, W: int, block_width: int,
+              with_order: bool, flags: int = 0):
+    """gstex_bin_sort into fresh buffers of n_isect pairs
+    -> (offsets, tile_ranges, sorted_ids, sorted_slots[, order])."""
     n = nth.shape[0]
     dev = nth.device
-    st = _stream(nth)
-    n_isect = pending if isinstance(pending, int) else _finish_count(pending)
     tiles_x = (W + block_width - 1) // block_width
     tiles_y = (H + block_width - 1) // block_width
     n_tiles = tiles_x * tiles_y
     tile_ranges = torch.empty((n_tiles, 2), device=dev, dtype=torch.int32)
     sorted_ids = torch.empty((n_isect,), device=dev, dtype=torch.int32)
     sorted_slots = torch.empty((n_isect,), device=dev, dtype=torch.int32)
+    order = torch.empty((n_tiles,), device=dev, dtype=torch.int32) if with_order else None
     wsb = int(_lib.load().gstex_bin_workspace_size(n, n_isect, n_tiles))
     bws = torch.empty((max(wsb, 1),), device=dev, dtype=torch.uint8)
     keep = [t.detach().contiguous() for t in (centers, extents, depths)]  # alive until the launch returns
-    geo = (ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), ptr(nth), ptr(offsets), int(H), int(W), int(block_width),
-           ptr(tile_ranges), ptr(sorted_ids), ptr(sorted_slots))
+    _launch("gstex_bin_sort", n, n_isect, ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), ptr(offsets), int(H), int(W),
+            int(block_width), ptr(tile_ranges), ptr(sorted_ids), ptr(sorted_slots), ptr(order), flags, ptr(bws),
+            bws.numel(), _stream(nth))
     if not with_order:
-        _launch("gstex_bin_sort", n, n_isect, *geo, ptr(bws), bws.numel(), st)
         return offsets, tile_ranges, sorted_ids, sorted_slots
-    order = torch.empty((n_tiles,), device=dev, dtype=torch.int32)
-    _launch("gstex_bin_sort_ordered", n, n_isect, *geo, ptr(order), ptr(bws), bws.numel(), st)
     return offsets, tile_ranges, sorted_ids, sorted_slots, order
+
+
+def bin_finish(begun, centers, extents, depths, H: int, W: int, block_width: int = BLOCK_WIDTH,
+               with_order: bool = False):
+    """Second half of bin_and_sort: wait for the pair count, size the pair buffers, bin and sort.  with_order:
+    also return the largest-first tile order the sort ranked (gstex_bin_sort's tile_order; == tile_order(ranges))."""
+    nth, offsets, pending = begun
+    n_isect = pending if isinstance(pending, int) else _finish_count(pending)
+    return _bin_sort(nth, offsets, n_isect, centers, extents, depths, H, W, block_width, with_order)
 
 
 class PairCapacity:
     """Read-back-free pair buffers for a training loop (ABI 13; replaces the per-render pair-count read-back of
     gstex.py:1045-1052, 1127 -- a device-to-host copy and a wait on it -- with buffers sized from a capacity).
 
-    Every render's scan writes its pair total on the device (gstex_scan_offsets_guarded): into the step's guard flag
+    Every render's scan writes its pair total on the device (gstex_scan_offsets' guard): into the step's guard flag
     (1.0 when the total exceeds the capacity; the binning then leaves every tile empty and the guarded Adam skips the
-    step's update, gstex_adam_step_guarded) and into one of RING device-writable host words, followed by a
+    step's update, gstex_adam_step's skip) and into one of RING device-writable host words, followed by a
     system-scope fence.  The host sets a slot's word to SENTINEL before the render is enqueued and reads the total once
     the word has changed -- no event in the stream (a recorded event cost ~5 us of device time per render), no copy, no
     synchronisation.  The capacity starts from one read-back of the first render's total (headroom x total + slack)
@@ -409,8 +412,7 @@ class PairCapacity:
         guard, k, cap = self.reserve(step_flag, first, tag, sized=False)
         offsets = torch.empty((n + 1,), device=nth.device, dtype=torch.int32)
         ws = torch.empty((max(int(_lib.load().gstex_scan_workspace_size(n)), 1),), device=nth.device, dtype=torch.uint8)
-        call("gstex_scan_offsets_guarded", n, ptr(nth), ptr(offsets), ptr(ws), ws.numel(), ctypes.byref(guard),
-             _stream(nth))
+        call("gstex_scan_offsets", n, ptr(nth), ptr(offsets), ptr(ws), ws.numel(), ctypes.byref(guard), _stream(nth))
         return offsets, self.commit(k, cap, tag, nth.device)
 
     def reserve(self, step_flag: torch.Tensor, first: bool, tag=None, sized: bool = True):
@@ -439,23 +441,8 @@ class PairCapacity:
 
 def bin_capped(nth, offsets, capacity: int, centers, extents, depths, H: int, W: int, block_width: int = BLOCK_WIDTH):
     """bin_finish without the host's pair count: buffers of `capacity` pairs, the total read on the device
-    (gstex_bin_sort_capped).  -> (offsets, tile_ranges, sorted_ids (capacity,), sorted_slots (capacity,), order)."""
-    n = nth.shape[0]
-    dev = nth.device
-    tiles_x = (W + block_width - 1) // block_width
-    tiles_y = (H + block_width - 1) // block_width
-    n_tiles = tiles_x * tiles_y
-    tile_ranges = torch.empty((n_tiles, 2), device=dev, dtype=torch.int32)
-    sorted_ids = torch.empty((capacity,), device=dev, dtype=torch.int32)
-    sorted_slots = torch.empty((capacity,), device=dev, dtype=torch.int32)
-    order = torch.empty((n_tiles,), device=dev, dtype=torch.int32)
-    bws = torch.empty((max(int(_lib.load().gstex_bin_workspace_size(n, capacity, n_tiles)), 1),), device=dev,
-                      dtype=torch.uint8)
-    keep = [t.detach().contiguous() for t in (centers, extents, depths)]
-    _launch("gstex_bin_sort_capped", n, capacity, ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), ptr(nth), ptr(offsets),
-            int(H), int(W), int(block_width), ptr(tile_ranges), ptr(sorted_ids), ptr(sorted_slots), ptr(order),
-            ptr(bws), bws.numel(), _stream(nth))
-    return offsets, tile_ranges, sorted_ids, sorted_slots, order
+    (GSTEX_BIN_CAPPED).  -> (offsets, tile_ranges, sorted_ids (capacity,), sorted_slots (capacity,), order)."""
+    return _bin_sort(nth, offsets, capacity, centers, extents, depths, H, W, block_width, True, _lib.BIN_CAPPED)
 
 
 def bin_and_sort(centers, extents, depths, num_tiles_hit, H: int, W: int, block_width: int = BLOCK_WIDTH):
@@ -551,7 +538,7 @@ class _TextureGaussians(torch.autograd.Function):
                        "texture_grad_sink must be a contiguous fp32 tensor shaped like texture on its device")
                 ctx.v_texture = texture_grad_sink
             else:
-                ctx.v_texture = torch.empty_like(texture)  # zeroed by the raster forward (gstex_raster_fwd_zero)
+                ctx.v_texture = torch.empty_like(texture)  # zeroed by the raster forward (its zero_buf)
         if before_pair_wait is not None:
             before_pair_wait()  # caller's work for the device while the host waits for the pair count
         if capped is not None:
@@ -602,52 +589,48 @@ class _TextureGaussians(torch.autograd.Function):
         # sums (PARTIAL_FLOATS per splat: room for either row width)
         zbuf = ctx.v_texture if (not ctx.sink or zero_sink) else None
         ctx.partials = torch.empty((n * PARTIAL_FLOATS,), device=dev, dtype=torch.float32) if needs_bwd else None
-        _launch("gstex_raster_fwd_zero", cam, C, int(settings), ptr(bg), ptr(records), ptr(hp), ptr(tile_ranges),
-                ptr(order),
-             ptr(sorted_ids),
-             ptr(texture), texture.shape[0], ctx_scale, ctx_bias, ptr(img), geo_ptrs[0], geo_ptrs[1], ptr(alpha),
-             ptr(tex), geo_ptrs[2],
-             ptr(state), n_isect, ptr(aux), ptr(zbuf), 0 if zbuf is None else zbuf.numel(), ptr(ctx.partials),
-             0 if ctx.partials is None else ctx.partials.numel(), st)
+        # what the forward and the backward share (the tensors behind the pointers are saved below)
+        scene = _lib.GstexRasterScene(
+            cam=cam, channels=C, settings=int(settings), background=ptr(bg), records=ptr(records),
+            hp_records=ptr(hp), tile_ranges=ptr(tile_ranges), sorted_ids=ptr(sorted_ids), texture=ptr(texture),
+            n_texels=texture.shape[0], tex_scale=ctx_scale, tex_bias=ctx_bias, state=ptr(state), n_isect=n_isect,
+            aux=ptr(aux))
+        fwd = _lib.GstexRasterFwdArgs(
+            scene=scene, tile_order=ptr(order), out_img=ptr(img), out_depth=geo_ptrs[0], out_reg=geo_ptrs[1],
+            out_alpha=ptr(alpha), out_tex=ptr(tex), out_normal=geo_ptrs[2],
+            zero_buf=ptr(zbuf), zero_floats=0 if zbuf is None else zbuf.numel(),
+            zero_buf2=ptr(ctx.partials), zero_floats2=0 if ctx.partials is None else ctx.partials.numel())
+        _launch("gstex_raster_fwd", ctypes.byref(fwd), st)
+        ctx.scene = scene
         ctx.aux = aux
-        ctx.save_for_backward(means, scales, quats, opacities, umap, vmap, texture, nth, offsets, tile_ranges,
-                              order, sorted_ids, sorted_slots, records, state, vm, cw if cw is not None else vm,
+        ctx.save_for_backward(means, scales, quats, umap, vmap, texture, nth, offsets, tile_ranges, sorted_ids,
+                              sorted_slots, records, state, vm, cw if cw is not None else vm,
                               bg if bg is not None else vm)
-        ctx.has_c2w = cw is not None
-        ctx.has_bg = bg is not None
-        ctx.args = (float(glob_scale), float(fx), float(fy), float(cx), float(cy), H, W, C, int(settings))
-        ctx.tex_affine = (ctx_scale, ctx_bias)
+        ctx.glob_scale = float(glob_scale)
         ctx.fold_aabb = bool(fold_aabb)
         ctx.set_materialize_grads(False)  # unused outputs' gradients stay None (no zero tensors)
         return img, depth, reg, alpha, tex, normal
 
     @staticmethod
     def backward(ctx, v_img, v_depth, v_reg, v_alpha, v_tex, v_normal):
-        (means, scales, quats, opacities, umap, vmap, texture, nth, offsets, tile_ranges, order, sorted_ids,
-         sorted_slots, records, state, vm, cw, bg) = ctx.saved_tensors
-        cw = cw if ctx.has_c2w else None
-        bg = bg if ctx.has_bg else None
-        glob, fx, fy, cx, cy, H, W, C, settings = ctx.args
+        (means, scales, quats, umap, vmap, texture, nth, offsets, tile_ranges, sorted_ids, sorted_slots, records,
+         state, vm, cw, bg) = ctx.saved_tensors  # (vm, cw, bg: alive behind the scene's pointers)
+        scene = ctx.scene
         n = means.shape[0]
         dev = means.device
         st = _stream(means)
-        cam = _lib.make_camera(vm, cw, fx, fy, cx, cy, H, W, BLOCK_WIDTH)
 
-        def g(t, shape):  # unused outputs arrive as None (no zero fill): the kernel reads NULL as zero
+        def g(t):  # unused outputs arrive as None (no zero fill): the kernel reads NULL as zero
             return None if t is None else t.contiguous()
 
-        v_img = g(v_img, (H, W, 3))
-        v_depth = g(v_depth, (H, W))
-        v_reg = g(v_reg, (H, W))
-        v_alpha = g(v_alpha, (H, W))
-        v_tex = g(v_tex, (H, W, C))
-        v_normal = g(v_normal, (H, W, 3))
+        v_img, v_depth, v_reg, v_alpha, v_tex, v_normal = (g(t) for t in (v_img, v_depth, v_reg, v_alpha, v_tex,
+                                                                          v_normal))
         n_isect = sorted_ids.shape[0]
         # 24 values per (pair, quadrant) sum without depth / normal / distortion gradients (gstex_raster_bwd), 32 with.
         # Default: float-atomic accumulation per splat (like the texel gradients).  Under
         # torch.use_deterministic_algorithms(True): one row per (pair, 8x8 quadrant), written only where the quadrant
         # contributes (row_flags), summed in a fixed order by setup_bwd -- bitwise reproducible splat gradients
-        geo = v_depth is not None or v_normal is not None or (v_reg is not None and bool(settings & (1 << 10)))
+        geo = v_depth is not None or v_normal is not None or (v_reg is not None and bool(scene.settings & (1 << 10)))
         row_floats = PARTIAL_FLOATS if geo else PARTIAL_FLOATS_PHOTO
         if torch.are_deterministic_algorithms_enabled():
             partials = torch.empty((n_isect, 4, row_floats), device=dev, dtype=torch.float32)
@@ -661,15 +644,15 @@ class _TextureGaussians(torch.autograd.Function):
             row_flags = None
         v_texture = ctx.v_texture if ctx.v_texture is not None else torch.zeros_like(texture)
         ctx.v_texture = None
-        _launch("gstex_raster_bwd", cam, C, int(settings), ptr(bg), ptr(records), ptr(ctx.hp),
-                ptr(tile_ranges),
-                ptr(sorted_ids), ptr(sorted_slots), ptr(texture), texture.shape[0], ctx.tex_affine[0],
-                ctx.tex_affine[1], ptr(state), ptr(v_img), ptr(v_depth), ptr(v_reg), ptr(v_alpha), ptr(v_tex),
-                ptr(v_normal), n_isect, ptr(partials), ptr(row_flags), ptr(v_texture), ptr(ctx.aux), st)
+        bwd = _lib.GstexRasterBwdArgs(
+            scene=scene, sorted_slots=ptr(sorted_slots), v_img=ptr(v_img), v_depth=ptr(v_depth), v_reg=ptr(v_reg),
+            v_alpha=ptr(v_alpha), v_tex=ptr(v_tex), v_normal=ptr(v_normal), partials=ptr(partials),
+            row_flags=ptr(row_flags), v_texture=ptr(v_texture))
+        _launch("gstex_raster_bwd", ctypes.byref(bwd), st)
         if PARTIALS_HOOK is not None:  # diagnostics (tools/hp_partials.py): the per-splat sums before the chain
             PARTIALS_HOOK(partials, row_flags, records, ctx.hp)
-        ctx.aux = None
-        ctx.hp = None
+        ctx.aux = ctx.hp = None  # released: a second backward of the same graph is refused (null aux)
+        scene.aux = scene.hp_records = None
         if ctx.sink:
             if ctx.on_texture_grad is not None:
                 ctx.on_texture_grad()  # the texel gradient is complete in stream order
@@ -681,10 +664,14 @@ class _TextureGaussians(torch.autograd.Function):
         v_opac = torch.empty((n, 1), device=dev, dtype=torch.float32)
         v_centers = torch.empty((n, 2), device=dev, dtype=torch.float32)
         v_uv0 = torch.empty((n, 1, 2), device=dev, dtype=torch.float32)
-        _launch("gstex_raster_setup_bwd_aabb" if ctx.fold_aabb else "gstex_raster_setup_bwd", n, ptr(means),
-                ptr(scales), glob, ptr(quats), ptr(opacities), ptr(umap), ptr(vmap), ptr(nth), ptr(offsets), ptr(partials),
-                ptr(row_flags), row_floats, n_isect if row_flags is not None else -1, cam,
-                ptr(v_means), ptr(v_scales), ptr(v_quats), ptr(v_rgbs), ptr(v_opac), ptr(v_centers), ptr(v_uv0), st)
+        sb = _lib.GstexRasterSetupBwdArgs(
+            n=n, glob_scale=ctx.glob_scale, row_floats=row_floats, fold_aabb=int(ctx.fold_aabb),
+            n_rows=n_isect if row_flags is not None else -1, cam=scene.cam, means=ptr(means), scales=ptr(scales),
+            quats=ptr(quats), umap=ptr(umap), vmap=ptr(vmap), num_tiles_hit=ptr(nth), offsets=ptr(offsets),
+            partials=ptr(partials), row_flags=ptr(row_flags), v_means=ptr(v_means), v_scales=ptr(v_scales),
+            v_quats=ptr(v_quats), v_rgbs=ptr(v_rgbs), v_opacities=ptr(v_opac), v_centers=ptr(v_centers),
+            v_uv0=ptr(v_uv0))
+        _launch("gstex_raster_setup_bwd", ctypes.byref(sb), st)
         v_bg = None
         if ctx.needs_input_grad[26]:
             v_bg = (v_img * state[..., 0:1]).sum((0, 1)) if v_img is not None else torch.zeros_like(bg)
@@ -709,7 +696,7 @@ def texture_gaussians(texture_info, texture_dims, centers, extents, depths, num_
 
     fold_aabb=True (not in the reference API; training path only) declares that `centers` came from
     get_aabb_2d(means, scales, glob_scale, quats, viewmat, (fx, fy, cx, cy)): the backward then chains the centre
-    gradient through the AABB itself (gstex_raster_setup_bwd_aabb) and returns none for `centers`, so neither
+    gradient through the AABB itself (gstex_raster_setup_bwd's fold_aabb) and returns none for `centers`, so neither
     get_aabb_2d's backward nor autograd's accumulation kernels run.  Same gradients, bit for bit.
 
     geometry_outputs=False (not in the reference API): depth, reg and normal are not produced (returned as

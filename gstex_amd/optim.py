@@ -23,11 +23,11 @@ class FusedAdam(torch.optim.Optimizer):
     def step(self, closure=None, only=None, skip=None, zero_grad=False, grid=0, grad_scale=1.0, skip_flag=None):
         """The Adam update.  Extensions (not in torch.optim.Adam): `only` / `skip` (sets of id(param)) restrict the
         update to / exclude a set of parameters (so one group can be launched on another stream), and `zero_grad` writes zeros over each
-        gradient after reading it (gstex_adam_step_ex, GSTEX_ADAM_ZERO_GRAD); `grid` > 0 caps the launch's
+        gradient after reading it (GSTEX_ADAM_ZERO_GRAD); `grid` > 0 caps the launch's
         workgroups (GSTEX_ADAM_GRID: each loops over the chunks), leaving CUs to another stream; `grad_scale` in (0, 1]
-        multiplies every gradient as it is read (gstex_adam_step_scaled: a data-parallel step's 1 / world, applied to the
+        multiplies every gradient as it is read (a data-parallel step's 1 / world, applied to the
         all-reduced sums -- bit-identical to averaging the buffer first); `skip_flag` (a 1-element device fp32 tensor)
-        makes the launch a no-op on the device when the value is non-zero (gstex_adam_step_guarded: the pair-capacity
+        makes the launch a no-op on the device when the value is non-zero (gstex_adam_step's skip: the pair-capacity
         guard of the step's renders, ops.PairCapacity) -- the step counts still advance, deliberately: the host learns
         of a skipped step only after the fact (no read-back in the step), so unlike GradScaler-style skipping (which
         does not call step() at all) the next real update applies the bias corrections of step t + 1 to moments last
@@ -109,13 +109,5 @@ class FusedAdam(torch.optim.Optimizer):
                 chunk = items[i:i + _lib.ADAM_MAX_TENSORS]
                 arr = (_lib.GstexAdamTensor * len(chunk))(*chunk)
                 flags = (_lib.ADAM_ZERO_GRAD if zero_grad else 0) | ((int(grid) & 0xFFFF) << _lib.ADAM_GRID_SHIFT)
-                if skip_flag is not None:
-                    _lib.call("gstex_adam_step_guarded", len(chunk), arr, float(b1), float(b2), float(eps), flags,
-                              float(grad_scale), _lib.ptr(skip_flag), st)
-                elif grad_scale != 1.0:
-                    _lib.call("gstex_adam_step_scaled", len(chunk), arr, float(b1), float(b2), float(eps), flags,
-                              float(grad_scale), st)
-                elif flags:
-                    _lib.call("gstex_adam_step_ex", len(chunk), arr, float(b1), float(b2), float(eps), flags, st)
-                else:
-                    _lib.call("gstex_adam_step", len(chunk), arr, float(b1), float(b2), float(eps), st)
+                _lib.call("gstex_adam_step", len(chunk), arr, float(b1), float(b2), float(eps), flags,
+                          float(grad_scale), _lib.ptr(skip_flag), st)

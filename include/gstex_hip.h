@@ -20,7 +20,8 @@
  *
  * Conventions
  *   - Every pointer is a DEVICE pointer to contiguous row-major fp32 / int32 memory, except
- *     `const gstex_camera*` which is a HOST struct (read at call time) of device pointers.
+ *     `const gstex_camera*` and the `*_args` structs, which are HOST structs (read at call time) of
+ *     device pointers.
  *   - `stream` is a hipStream_t (NULL = default stream). Calls only enqueue work: no allocation,
  *     no host synchronisation.
  *   - Scratch memory is caller-owned: query the size with the *_workspace_size function, allocate
@@ -38,9 +39,14 @@
 extern "C" {
 #endif
 
-/* ABI 18 (round 6): the hipGraph step support of ABI 16 (event-record nodes, gstex_adam_step_scheduled) and the
+/* ABI 19: one exported symbol per operation.  The variant entry points of ABI 7-17 are folded into their base calls as
+ * nullable arguments, flags or struct fields: gstex_raster_fwd / gstex_raster_bwd take argument structs (the _zero
+ * variants' buffers are fields; aux_zeroed replaces the settings bit 28), gstex_raster_setup_bwd takes a struct with
+ * fold_aabb (was _aabb), gstex_bin_sort takes tile_order and flags (was _ordered, _capped), gstex_scan_offsets takes a
+ * nullable guard (was _guarded), gstex_adam_step takes flags, grad_scale and skip (was _ex, _scaled, _guarded).
+ * ABI 18 (round 6): the hipGraph step support of ABI 16 (event-record nodes, gstex_adam_step_scheduled) and the
  * split-backward settings bit of ABI 15 are removed (measured slower). */
-#define GSTEX_ABI_VERSION 18
+#define GSTEX_ABI_VERSION 19
 
 /* Per-record layout of the splat table written by gstex_raster_setup (floats). */
 #define GSTEX_REC_FLOATS 32
@@ -55,10 +61,6 @@ extern "C" {
 #define GSTEX_SETTING_DIST_REG (1 << 10) /* 2DGS NDC depth-distortion output */
 #define GSTEX_SETTING_EDIT (1 << 13)     /* texture_edit request (gstex.py:599) */
 #define GSTEX_SETTING_EVAL_NORMAL (1 << 15) /* eval normal/edit render (gstex.py:1198): normal output unit-length, forward only */
-/* gstex_raster_fwd / gstex_raster_fwd_zero only (ABI 17): the aux span the forward accumulates its unit costs, launch
- * order and unit-order histogram into was zeroed by gstex_train_prologue (args.raster_aux, same n_isect / tiles /
- * channels) on the same stream, so the forward skips its own fill.  Set it only after such a prologue call. */
-#define GSTEX_SETTING_AUX_ZEROED (1 << 28)
 
 typedef enum {
     GSTEX_OK = 0,
@@ -101,48 +103,24 @@ int gstex_num_tiles_hit(int32_t n, const float* centers, const float* extents, i
 /* The three preprocessing outputs a render needs, in one pass (ABI 10): depths[n] (the view depth of
  * gstex_project_points), centers / extents[n][2] (gstex_aabb_2d) and num_tiles_hit[n]
  * (gstex_num_tiles_hit with cam->H, cam->W, cam->block), bit-identical to the three calls.  No
- * backward: a caller that needs the centre gradient uses gstex_raster_setup_bwd_aabb (fold). */
+ * backward: a caller that needs the centre gradient uses gstex_raster_setup_bwd with fold_aabb. */
 int gstex_preprocess(int32_t n, const float* means, const float* scales, float glob_scale,
                      const float* quats, const gstex_camera* cam, float* depths, float* centers,
                      float* extents, int32_t* num_tiles_hit, void* stream);
 
 /* ---- binning + per-tile depth sort ---------------------------------------------------- */
 size_t gstex_scan_workspace_size(int32_t n);
-/* offsets[0..n] = exclusive prefix sum of num_tiles_hit; offsets[n] = total intersections. */
-int gstex_scan_offsets(int32_t n, const int32_t* num_tiles_hit, int32_t* offsets,
-                       void* workspace, size_t workspace_bytes, void* stream);
-size_t gstex_bin_workspace_size(int32_t n, int64_t n_isect, int32_t n_tiles);
-/* Emits one (tile, splat) pair per covered tile, buckets them per tile and sorts every tile's
- * list by (depth bits, splat id).  Outputs: tile_ranges[n_tiles][2] = [start, end) into
- * sorted_ids; sorted_ids[n_isect] = splat id; sorted_slots[n_isect] = emission index
- * offsets[id] + k (k = row-major rank of the tile inside the splat's tile rectangle). */
-int gstex_bin_sort(int32_t n, int64_t n_isect, const float* centers, const float* extents,
-                   const float* depths, const int32_t* num_tiles_hit, const int32_t* offsets,
-                   int32_t H, int32_t W, int32_t block, int32_t* tile_ranges,
-                   int32_t* sorted_ids, int32_t* sorted_slots, void* workspace,
-                   size_t workspace_bytes, void* stream);
-/* gstex_bin_sort that also writes tile_order[n_tiles] (non-NULL), the largest-first launch order
- * gstex_tile_order would compute from the resulting tile_ranges (same keys, same ranking): the
- * tile sort already ranks the buckets, so the raster forward reuses that order instead of a
- * second ranking launch.  ABI 8. */
-int gstex_bin_sort_ordered(int32_t n, int64_t n_isect, const float* centers, const float* extents,
-                           const float* depths, const int32_t* num_tiles_hit, const int32_t* offsets,
-                           int32_t H, int32_t W, int32_t block, int32_t* tile_ranges,
-                           int32_t* sorted_ids, int32_t* sorted_slots, int32_t* tile_order,
-                           void* workspace, size_t workspace_bytes, void* stream);
-
-/* ---- read-back-free binning (ABI 13) -------------------------------------------------------
- * The reference sizes its pair buffers from the pair total on the host (gstex.py:1045-1052, 1127: a device-to-host
- * read and a stream synchronisation every render).  Capacity mode sizes them from a capacity instead and keeps the
- * total on the device:
- *   gstex_scan_offsets_guarded: gstex_scan_offsets, and the thread that writes the total offsets[n] also writes
+/* Read-back-free binning (ABI 13).  The reference sizes its pair buffers from the pair total on the host
+ * (gstex.py:1045-1052, 1127: a device-to-host read and a stream synchronisation every render).  Capacity mode sizes
+ * them from a capacity instead and keeps the total on the device:
+ *   gstex_scan_offsets with a guard: the thread that writes the total offsets[n] also writes
  *     *step_flag = (total > capacity) ? 1.0f : 0.0f (first != 0: the step's first render; otherwise the larger of
  *     the two) and, when host_count != NULL, the total into host_count -- memory the device can write and the host
  *     reads (pinned, mapped) once the stream has passed the scan: no copy, no synchronisation;
- *   gstex_bin_sort_capped: gstex_bin_sort_ordered with n_isect = the capacity (buffers, workspace); the kernels read
+ *   gstex_bin_sort with GSTEX_BIN_CAPPED: n_isect = the capacity (buffers, workspace); the kernels read
  *     the total from offsets[n], and a total above the capacity leaves every tile empty (nothing is written past the
  *     buffers);
- *   gstex_adam_step_guarded: gstex_adam_step_scaled that does nothing when *skip != 0 (an overflowed step's update
+ *   gstex_adam_step with skip: does nothing when *skip != 0 (an overflowed step's update
  *     is skipped on the device; the host grows the capacity when it sees the total).
  * The raster entry points take the capacity as n_isect (it only sizes the aux layout and the backward's grid, whose
  * surplus units exit at once). */
@@ -152,6 +130,30 @@ typedef struct gstex_pair_guard {
     int32_t* host_count; /* nullable */
     int32_t first;
 } gstex_pair_guard;
+/* offsets[0..n] = exclusive prefix sum of num_tiles_hit; offsets[n] = total intersections.  guard (ABI 13; nullable =
+ * the plain scan): the pair-capacity guard above, capacity >= 0. */
+int gstex_scan_offsets(int32_t n, const int32_t* num_tiles_hit, int32_t* offsets,
+                       void* workspace, size_t workspace_bytes, const gstex_pair_guard* guard, void* stream);
+size_t gstex_bin_workspace_size(int32_t n, int64_t n_isect, int32_t n_tiles);
+/* Emits one (tile, splat) pair per covered tile, buckets them per tile and sorts every tile's
+ * list by (depth bits, splat id).  Outputs: tile_ranges[n_tiles][2] = [start, end) into
+ * sorted_ids; sorted_ids[n_isect] = splat id; sorted_slots[n_isect] = emission index
+ * offsets[id] + k (k = row-major rank of the tile inside the splat's tile rectangle).
+ * tile_order (ABI 8; nullable = not written): tile_order[n_tiles], the largest-first launch order
+ * gstex_tile_order would compute from the resulting tile_ranges (same keys, same ranking): the
+ * tile sort already ranks the buckets, so the raster forward reuses that order instead of a
+ * second ranking launch.
+ * flags: GSTEX_BIN_CAPPED (ABI 13; needs tile_order): n_isect is the pair buffers' capacity and the total is read on
+ * the device, see above.  GSTEX_BIN_COUNT_ZEROED: the caller has already zeroed the workspace's per-tile pair counters
+ * on the stream (gstex_train_prologue does, inside its scan kernel), so no fill is launched.  Other bits are
+ * rejected. */
+#define GSTEX_BIN_CAPPED 1
+#define GSTEX_BIN_COUNT_ZEROED 2
+int gstex_bin_sort(int32_t n, int64_t n_isect, const float* centers, const float* extents,
+                   const float* depths, const int32_t* offsets,
+                   int32_t H, int32_t W, int32_t block, int32_t* tile_ranges,
+                   int32_t* sorted_ids, int32_t* sorted_slots, int32_t* tile_order, int32_t flags,
+                   void* workspace, size_t workspace_bytes, void* stream);
 /* n device-writable host words (hipHostMalloc, mapped; zeroed): *host for the host, *device for
  * gstex_pair_guard.host_count.  Freed with gstex_host_words_free(host). */
 int gstex_host_words_alloc(int32_t n, int32_t** host, int32_t** device);
@@ -170,13 +172,6 @@ int gstex_event_record(void* event, void* stream);
 int gstex_event_elapsed(void* start, void* end, float* ms);
 int gstex_stream_wait_event(void* stream, void* event);
 int gstex_event_destroy(void* event);
-int gstex_scan_offsets_guarded(int32_t n, const int32_t* num_tiles_hit, int32_t* offsets, void* workspace,
-                               size_t workspace_bytes, const gstex_pair_guard* guard, void* stream);
-int gstex_bin_sort_capped(int32_t n, int64_t capacity, const float* centers, const float* extents,
-                          const float* depths, const int32_t* num_tiles_hit, const int32_t* offsets,
-                          int32_t H, int32_t W, int32_t block, int32_t* tile_ranges, int32_t* sorted_ids,
-                          int32_t* sorted_slots, int32_t* tile_order, void* workspace, size_t workspace_bytes,
-                          void* stream);
 
 /* Largest-first launch order of the tiles: tile_order[n_tiles] lists the tiles by descending
  * pair count (ties by tile index).  Pass it to gstex_raster_fwd / gstex_texture_edit, whose
@@ -190,8 +185,8 @@ int gstex_tile_order(int32_t n_tiles, const int32_t* tile_ranges, int32_t* tile_
  * hp_records (ABI 18; nullable = none): a device double[n][GSTEX_HP_DOUBLES] buffer.  A splat whose normal is within
  * ~6 degrees of edge-on to its view direction (|n . d| < 0.1) is then marked near edge-on -- the sign bit of its
  * record opacity is set (every kernel reads the magnitude) -- and its row g receives the fp64 affine homography (A, B,
- * Pz), anchor and depth row; other rows are not written.  Pass the same buffer to gstex_raster_fwd(_zero) and
- * gstex_raster_bwd(_zero), which evaluate those splats' pairs from it (the offset from the anchor and the homogeneous
+ * Pz), anchor and depth row; other rows are not written.  Pass the same buffer to gstex_raster_fwd and
+ * gstex_raster_bwd, which evaluate those splats' pairs from it (the offset from the anchor and the homogeneous
  * point in fp64, rounded once: their fp32 evaluation is ill-conditioned).  gstex_texture_edit ignores
  * the marks (pass records built without hp_records). */
 int gstex_raster_setup(int32_t n, const float* means, const float* scales, float glob_scale,
@@ -200,41 +195,60 @@ int gstex_raster_setup(int32_t n, const float* means, const float* scales, float
                        const float* vmap, const int32_t* texture_dims,
                        const int32_t* num_tiles_hit, const gstex_camera* cam, float* records,
                        double* hp_records, void* stream);
-/* Texel values: the texels are read as tex_scale * texture + tex_bias (1, 0 = as stored), so a caller
- * that keeps SH-DC coefficients (gstex.py:1119 passes SH2RGB(texture_dc) = 0.28209 x + 0.5) can pass the
- * store itself; the backward's v_texture is then the gradient w.r.t. the stored values. */
-/* Forward composite. Outputs are [H][W][k] row-major. state[H*W][4] = {T_final, M1, M2,
- * last_contributor (as int bits)} is saved for the backward pass. background is a device
- * float[3] (or NULL = black) added as T_final * background.  out_depth, out_reg and out_normal may be
- * NULL together (geometric outputs not produced; the backward then takes no gradient for them).
- * aux (NULL = no backward follows): a gstex_raster_aux_bytes(n_isect, n_tiles, channels) device workspace the
- * forward fills for the backward -- its per-wave cull bits (per tile, 8x8 pixel quadrant and tile-list position),
- * per backward unit (tile, quadrant, segment of 256 list positions) the number of splats it evaluated, and
- * per-pixel checkpoints (transmittance and accumulators) at the segment boundaries of deep lists.  Pass the same
- * aux, untouched, to gstex_raster_bwd.
- * hp_records (ABI 18, nullable): gstex_raster_setup's near-edge-on rows -- the marked splats' pairs are then evaluated
- * from them (p in fp64, rounded once); pass the same buffer to the backward, which must take the same decisions.
- * NULL: every pair from the fp32 record (the marks ignored). */
-int gstex_raster_fwd(const gstex_camera* cam, int32_t channels, int32_t settings,
-                     const float* background, const float* records, const double* hp_records,
-                     const int32_t* tile_ranges,
-                     const int32_t* tile_order, const int32_t* sorted_ids, const float* texture,
-                     int64_t n_texels, float tex_scale, float tex_bias,
-                     float* out_img, float* out_depth, float* out_reg, float* out_alpha,
-                     float* out_tex, float* out_normal, float* state, int64_t n_isect, void* aux,
-                     void* stream);
-/* The same, also zeroing zero_buf[0, zero_floats) and zero_buf2[0, zero_floats2) (ABI 11; NULL / 0 = none): the
- * buffers the backward accumulates into (the texel gradient, the fast mode's per-splat partials), cleared by the
- * forward's grid with streaming stores the raster work hides (no separate fills). */
-int gstex_raster_fwd_zero(const gstex_camera* cam, int32_t channels, int32_t settings,
-                          const float* background, const float* records, const double* hp_records,
-                          const int32_t* tile_ranges,
-                          const int32_t* tile_order, const int32_t* sorted_ids, const float* texture,
-                          int64_t n_texels, float tex_scale, float tex_bias,
-                          float* out_img, float* out_depth, float* out_reg, float* out_alpha,
-                          float* out_tex, float* out_normal, float* state, int64_t n_isect, void* aux,
-                          float* zero_buf, int64_t zero_floats, float* zero_buf2, int64_t zero_floats2,
-                          void* stream);
+/* What the raster forward and its backward share (ABI 19): a caller fills it once for the forward and hands the same
+ * value to the backward.  The argument structs are HOST structs of device pointers, read at call time. */
+typedef struct gstex_raster_scene {
+    gstex_camera cam;
+    int32_t channels;        /* texture channels C, in [1, 8] */
+    int32_t settings;        /* the reference's settings bits (GSTEX_SETTING_*); anything else is rejected */
+    const float* background; /* a device float[3] (or NULL = black) added as T_final * background */
+    const float* records;    /* gstex_raster_setup's table */
+    const double* hp_records; /* nullable (ABI 18): gstex_raster_setup's near-edge-on rows -- the marked splats' pairs
+                                 are then evaluated from them (p in fp64, rounded once); the backward must take the
+                                 same decisions.  NULL: every pair from the fp32 record (the marks ignored). */
+    const int32_t* tile_ranges;
+    const int32_t* sorted_ids;
+    const float* texture;    /* Texel values: the texels are read as tex_scale * texture + tex_bias (1, 0 = as stored),
+                                so a caller that keeps SH-DC coefficients (gstex.py:1119 passes SH2RGB(texture_dc) =
+                                0.28209 x + 0.5) can pass the store itself; the backward's v_texture is then the
+                                gradient w.r.t. the stored values. */
+    int64_t n_texels;
+    float tex_scale;
+    float tex_bias;
+    float* state;            /* state[H*W][4] = {T_final, M1, M2, last_contributor (as int bits)}: written by the
+                                forward, read by the backward */
+    int64_t n_isect;         /* pairs in sorted_ids (capacity mode: the capacity) */
+    void* aux;               /* forward: NULL = no backward follows; backward: required.  A gstex_raster_aux_bytes(
+                                n_isect, n_tiles, channels) device workspace the forward fills for the backward -- its
+                                per-wave cull bits (per tile, 8x8 pixel quadrant and tile-list position), per backward
+                                unit (tile, quadrant, segment of 256 list positions) the number of splats it evaluated,
+                                and per-pixel checkpoints (transmittance and accumulators) at the segment boundaries of
+                                deep lists -- and the backward writes its launch order into.  Untouched in between. */
+} gstex_raster_scene;
+/* Forward composite. Outputs are [H][W][k] row-major.  out_depth, out_reg and out_normal may be
+ * NULL together (geometric outputs not produced; the backward then takes no gradient for them). */
+typedef struct gstex_raster_fwd_args {
+    gstex_raster_scene scene;
+    const int32_t* tile_order; /* nullable = row-major (gstex_tile_order) */
+    float* out_img;
+    float* out_depth;
+    float* out_reg;
+    float* out_alpha;
+    float* out_tex;
+    float* out_normal;
+    /* zero_buf[0, zero_floats) and zero_buf2[0, zero_floats2) are zeroed too (ABI 11; NULL / 0 = none): the buffers the
+     * backward accumulates into (the texel gradient, the fast mode's per-splat partials), cleared by the forward's grid
+     * with streaming stores the raster work hides (no separate fills). */
+    float* zero_buf;
+    int64_t zero_floats;
+    float* zero_buf2;
+    int64_t zero_floats2;
+    int32_t aux_zeroed;      /* non-zero (ABI 17; was settings bit 28): the aux span the forward accumulates its unit
+                                costs, launch order and unit-order histogram into was zeroed by gstex_train_prologue
+                                (args.raster_aux, same n_isect / tiles / channels) on the same stream, so the forward
+                                skips its own fill.  Set it only after such a prologue call. */
+} gstex_raster_fwd_args;
+int gstex_raster_fwd(const gstex_raster_fwd_args* args, void* stream);
 size_t gstex_raster_aux_bytes(int64_t n_isect, int32_t n_tiles, int32_t channels);
 /* Launch order of n_units backward units: unit_key = cost (bits 0-23, clamped to 1023) | XCD group (bits 24-26).
  * Units of cost 0 get no position; the others are sorted by descending cost within their group and the groups
@@ -253,59 +267,67 @@ size_t gstex_unit_order_scratch_words(void);
  * never written) and sets byte q of row_flags[s] (n_isect uint32 words, zeroed by this call on the stream);
  * accumulates (+=) texel gradients into v_texture[n_texels][C].  R = GSTEX_PARTIAL_FLOATS_PHOTO (24) when neither
  * v_depth nor v_normal is given and v_reg is NULL or distortion (settings bit 10) is off -- the photometric training
- * step -- else GSTEX_PARTIAL_FLOATS (32); pass the same R to gstex_raster_setup_bwd(_aabb) as row_floats.
+ * step -- else GSTEX_PARTIAL_FLOATS (32); pass the same R to gstex_raster_setup_bwd as row_floats.
  * row_flags == NULL (ABI 9, the fast mode): instead of rows, every (pair, quadrant) sum is added with float
  * atomics into partials[g * R ...], an (n_splats, R) accumulator the caller has zeroed -- no per-pair rows, no
  * summing pass in setup_bwd; the splat gradients then depend on the atomics' order in their last bits (as the
- * texel gradients always do).  With row_flags the splat gradients are bitwise reproducible.
- * hp_records (ABI 18, nullable): the forward's hp_records (the same pairs evaluated the same way). */
-int gstex_raster_bwd(const gstex_camera* cam, int32_t channels, int32_t settings,
-                     const float* background, const float* records, const double* hp_records,
-                     const int32_t* tile_ranges,
-                     const int32_t* sorted_ids, const int32_t* sorted_slots, const float* texture,
-                     int64_t n_texels, float tex_scale, float tex_bias, const float* state,
-                     const float* v_img, const float* v_depth, const float* v_reg, const float* v_alpha,
-                     const float* v_tex, const float* v_normal, int64_t n_isect, float* partials,
-                     uint32_t* row_flags, float* v_texture, void* aux, void* stream);
-/* gstex_raster_bwd that also zeroes zero_buf[0, zero_floats) with its grid (ABI 17): a persistent gradient buffer of
- * the NEXT step (gstex_amd.fused double-buffers the texel gradient: this backward accumulates into v_texture and zeroes
- * the other buffer, which the next step's backward accumulates into) -- instead of the forward's zeroing
- * (gstex_raster_fwd_zero).  zero_buf must not be v_texture. */
-int gstex_raster_bwd_zero(const gstex_camera* cam, int32_t channels, int32_t settings, const float* background,
-                          const float* records, const double* hp_records, const int32_t* tile_ranges,
-                          const int32_t* sorted_ids,
-                          const int32_t* sorted_slots, const float* texture, int64_t n_texels, float tex_scale,
-                          float tex_bias, const float* state, const float* v_img, const float* v_depth,
-                          const float* v_reg, const float* v_alpha, const float* v_tex, const float* v_normal,
-                          int64_t n_isect, float* partials, uint32_t* row_flags, float* v_texture, void* aux,
-                          float* zero_buf, int64_t zero_floats, void* stream);
+ * texel gradients always do).  With row_flags the splat gradients are bitwise reproducible. */
+typedef struct gstex_raster_bwd_args {
+    gstex_raster_scene scene; /* the forward's (hp_records included: the same pairs evaluated the same way) */
+    const int32_t* sorted_slots;
+    const float* v_img;
+    const float* v_depth;
+    const float* v_reg;
+    const float* v_alpha;
+    const float* v_tex;
+    const float* v_normal;   /* must be NULL with settings bit 15 (the unit-normal eval render has no gradient) */
+    float* partials;
+    uint32_t* row_flags;     /* nullable = the fast mode */
+    float* v_texture;
+    /* zero_buf[0, zero_floats) is zeroed by the backward's grid (ABI 17; NULL / 0 = none): a persistent gradient
+     * buffer of the NEXT step (gstex_amd.fused double-buffers the texel gradient: this backward accumulates into
+     * v_texture and zeroes the other buffer, which the next step's backward accumulates into) -- instead of the
+     * forward's zeroing (gstex_raster_fwd_args.zero_buf).  zero_buf must not be v_texture. */
+    float* zero_buf;
+    int64_t zero_floats;
+} gstex_raster_bwd_args;
+int gstex_raster_bwd(const gstex_raster_bwd_args* args, void* stream);
 /* Sums each splat's flagged partial rows (slot-major, quadrant-minor order: bitwise reproducible) and chains
  * them to the splat parameters. Outputs are overwritten.  partials is consumed: each splat's sums are written
- * over its first row (the rows are backward scratch, not read again).  row_flags == NULL: partials is the
- * backward's (n, row_floats) per-splat accumulator (gstex_raster_bwd without row_flags), chained directly.
- * n_rows (ABI 15): the pair capacity the rows were allocated for (n_rows * 4 rows), or -1 when offsets[n] is
- * known to fit; with capacity-sized pair buffers (gstex_bin_sort_capped) a total offsets[n] > n_rows means the
- * binning left every tile empty, and every splat is then chained as pair-free (zero gradients) without reading
- * rows past the allocation. */
-int gstex_raster_setup_bwd(int32_t n, const float* means, const float* scales, float glob_scale,
-                           const float* quats, const float* opacities, const float* umap,
-                           const float* vmap, const int32_t* num_tiles_hit,
-                           const int32_t* offsets, float* partials, const uint32_t* row_flags,
-                           int32_t row_floats, int64_t n_rows, const gstex_camera* cam, float* v_means, float* v_scales,
-                           float* v_quats, float* v_rgbs, float* v_opacities, float* v_centers,
-                           float* v_uv0, void* stream);
-/* gstex_raster_setup_bwd with gstex_aabb_2d_bwd folded in: for callers whose centres came from
- * gstex_aabb_2d on these same means / scales / quats (glob_scale, camera), the centre gradient is chained
- * through the AABB centre here and added to v_means / v_scales / v_quats (bit-identical to running
- * gstex_aabb_2d_bwd separately and adding the two results); v_centers is still written. */
-int gstex_raster_setup_bwd_aabb(int32_t n, const float* means, const float* scales, float glob_scale,
-                                const float* quats, const float* opacities, const float* umap,
-                                const float* vmap, const int32_t* num_tiles_hit,
-                                const int32_t* offsets, float* partials, const uint32_t* row_flags,
-                                int32_t row_floats, int64_t n_rows, const gstex_camera* cam, float* v_means,
-                                float* v_scales,
-                                float* v_quats, float* v_rgbs, float* v_opacities, float* v_centers,
-                                float* v_uv0, void* stream);
+ * over its first row (the rows are backward scratch, not read again). */
+typedef struct gstex_raster_setup_bwd_args {
+    int32_t n;
+    float glob_scale;
+    int32_t row_floats;      /* the raster backward's R */
+    int32_t fold_aabb;       /* non-zero: gstex_aabb_2d_bwd folded in -- for callers whose centres came from
+                                gstex_aabb_2d on these same means / scales / quats (glob_scale, camera), the centre
+                                gradient is chained through the AABB centre here and added to v_means / v_scales /
+                                v_quats (bit-identical to running gstex_aabb_2d_bwd separately and adding the two
+                                results); v_centers is still written. */
+    int64_t n_rows;          /* ABI 15: the pair capacity the rows were allocated for (n_rows * 4 rows), or -1 when
+                                offsets[n] is known to fit; with capacity-sized pair buffers (GSTEX_BIN_CAPPED) a total
+                                offsets[n] > n_rows means the binning left every tile empty, and every splat is then
+                                chained as pair-free (zero gradients) without reading rows past the allocation. */
+    gstex_camera cam;
+    const float* means;
+    const float* scales;
+    const float* quats;
+    const float* umap;
+    const float* vmap;
+    const int32_t* num_tiles_hit;
+    const int32_t* offsets;
+    float* partials;
+    const uint32_t* row_flags; /* NULL: partials is the backward's (n, row_floats) per-splat accumulator
+                                  (gstex_raster_bwd without row_flags), chained directly */
+    float* v_means;
+    float* v_scales;
+    float* v_quats;
+    float* v_rgbs;
+    float* v_opacities;
+    float* v_centers;
+    float* v_uv0;
+} gstex_raster_setup_bwd_args;
+int gstex_raster_setup_bwd(const gstex_raster_setup_bwd_args* args, void* stream);
 
 /* ---- spherical harmonics (degree <= 4) ------------------------------------------------- */
 int gstex_sh_fwd(int32_t n, int32_t degree, int32_t n_coeffs, const float* viewdirs,
@@ -385,36 +407,31 @@ typedef struct gstex_adam_tensor {
     float step_size;
     float bias_correction2_sqrt;
 } gstex_adam_tensor;
-int gstex_adam_step(int32_t n_tensors, const gstex_adam_tensor* tensors, double beta1, double beta2,
-                    double eps, void* stream);
-/* gstex_adam_step with flags: GSTEX_ADAM_ZERO_GRAD also writes zeros over each gradient after reading it (so the
- * next backward can accumulate into the same buffer without a separate fill; the update may then run on a side
- * stream, overlapped with the next step's preprocessing).  Not in the reference (torch.optim.Adam + zero_grad). */
+/* flags (0 = the reference's update; unknown bits are rejected): GSTEX_ADAM_ZERO_GRAD also writes zeros over each
+ * gradient after reading it (so the next backward can accumulate into the same buffer without a separate fill; the
+ * update may then run on a side stream, overlapped with the next step's preprocessing).  Not in the reference
+ * (torch.optim.Adam + zero_grad). */
 #define GSTEX_ADAM_ZERO_GRAD 1
 /* flags bits 8..23: cap on the launch's workgroups (0 = one per 1024 elements), each looping over the chunks; a
  * capped grid (e.g. one workgroup per CU) still streams at near full HBM bandwidth while leaving most of every CU's
  * wave slots to kernels of another stream.  GSTEX_ADAM_GRID(n) builds the field. */
 #define GSTEX_ADAM_GRID_SHIFT 8
 #define GSTEX_ADAM_GRID(n) (((n) & 0xFFFF) << GSTEX_ADAM_GRID_SHIFT)
-int gstex_adam_step_ex(int32_t n_tensors, const gstex_adam_tensor* tensors, double beta1, double beta2,
-                       double eps, int32_t flags, void* stream);
-/* gstex_adam_step_ex with every gradient read as grad * grad_scale, grad_scale in (0, 1] (ABI 7): a data-parallel
+/* grad_scale in (0, 1] (ABI 7; 1 = none): every gradient is read as grad * grad_scale -- a data-parallel
  * step passes 1 / world_size and skips the separate averaging pass over the all-reduced gradient buffer (the same
  * fp32 product, so the update is bit-identical).  Replaces, with GStex's GradSync, the 1 / world averaging of the
- * reference's DDP (pipelines/base_pipeline.py:281-283). */
-int gstex_adam_step_scaled(int32_t n_tensors, const gstex_adam_tensor* tensors, double beta1, double beta2,
-                           double eps, int32_t flags, float grad_scale, void* stream);
-/* gstex_adam_step_scaled that reads *skip (a device float, nullable = never) first and updates nothing when it is
- * non-zero: the pair-capacity guard's step flag (gstex_scan_offsets_guarded), all-reduced with the gradients in
- * data-parallel training so that every rank skips the same steps.  ABI 13. */
-int gstex_adam_step_guarded(int32_t n_tensors, const gstex_adam_tensor* tensors, double beta1, double beta2,
-                            double eps, int32_t flags, float grad_scale, const float* skip, void* stream);
+ * reference's DDP (pipelines/base_pipeline.py:281-283).
+ * skip (ABI 13; a device float, nullable = never): read first, and nothing is updated when it is
+ * non-zero: the pair-capacity guard's step flag (gstex_scan_offsets with a guard), all-reduced with the gradients in
+ * data-parallel training so that every rank skips the same steps. */
+int gstex_adam_step(int32_t n_tensors, const gstex_adam_tensor* tensors, double beta1, double beta2,
+                    double eps, int32_t flags, float grad_scale, const float* skip, void* stream);
 
 /* ---- training-step prologue (ABI 17; not in the reference) ------------------------------------------------------
  * One host call for the launches a photometric training render makes before its raster forward: the outputs of
- * gstex_activate_fwd, gstex_preprocess (the camera without c2w), gstex_sh_rest_fwd and gstex_scan_offsets_guarded --
- * bit-identical, computed by one per-splat kernel (the same device functions on the same values) and a one-launch
- * scan -- then gstex_raster_setup (glob_scale 1) and gstex_bin_sort_capped as called per op (gstex_amd.fused: the
+ * gstex_activate_fwd, gstex_preprocess (the camera without c2w), gstex_sh_rest_fwd and the guarded gstex_scan_offsets
+ * -- bit-identical, computed by one per-splat kernel (the same device functions on the same values) and a one-launch
+ * scan -- then gstex_raster_setup (glob_scale 1) and the capped gstex_bin_sort as called per op (gstex_amd.fused: the
  * trainer's render without ~0.2 ms of per-launch host overhead, which a step that starts on an idle device waits for,
  * and four launches fewer).  All pointers are device pointers; the buffers are sized as the per-op entry points
  * require (block = 16), scan_workspace as gstex_train_prologue_scan_bytes(n). */
@@ -457,8 +474,8 @@ typedef struct gstex_train_prologue_args {
     void* bin_workspace;
     size_t bin_workspace_bytes;
     void* raster_aux;        /* nullable: the raster forward's aux buffer (gstex_raster_aux_bytes(capacity, n_tiles,
-                                raster_channels)), whose accumulated span the prologue zeroes -- pass
-                                GSTEX_SETTING_AUX_ZEROED to the forward that follows */
+                                raster_channels)), whose accumulated span the prologue zeroes -- set
+                                aux_zeroed in the args of the forward that follows */
     size_t raster_aux_bytes;
     int32_t raster_channels;
     double* hp_records;      /* nullable (ABI 18): gstex_raster_setup's near-edge-on fp64 rows, double[n][12] */
@@ -469,9 +486,9 @@ int gstex_train_prologue(const gstex_train_prologue_args* args, void* stream);
 size_t gstex_train_prologue_scan_bytes(int32_t n);
 
 /* The photometric training render's backward after gstex_raster_bwd (fast mode: partials = the zeroed (n, 24)
- * per-splat accumulator rows it added into), in one call (ABI 17; gstex_amd.fused): gstex_raster_setup_bwd_aabb
- * (glob_scale 1, the camera with c2w), then gstex_activate_bwd and gstex_sh_rest_bwd on its outputs -- one kernel, the
- * same device functions on the same values (bit-identical), when the SH rows fit its LDS staging.  v_* are the
+ * per-splat accumulator rows it added into), in one call (ABI 17; gstex_amd.fused): gstex_raster_setup_bwd
+ * (fold_aabb, glob_scale 1, the camera with c2w), then gstex_activate_bwd and gstex_sh_rest_bwd on its outputs -- one
+ * kernel, the same device functions on the same values (bit-identical), when the SH rows fit its LDS staging.  v_* are the
  * parameter gradients (written, not accumulated); v_*_act and v_centers / v_uv0 are scratch of n rows each (the
  * activated parameters' gradients, as the per-op calls write them). */
 typedef struct gstex_train_epilogue_args {

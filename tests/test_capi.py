@@ -34,10 +34,15 @@ def test_every_header_symbol_is_exported_and_bound(lib):
         assert hasattr(lib, s), f"{s} declared in gstex_hip.h but not exported"
         assert s in _lib.SIGNATURES, f"{s} has no ctypes signature in gstex_amd/_lib.py"
     assert set(_lib.SIGNATURES) == set(syms), "ctypes signatures out of sync with the header"
+    # ABI 19: the variant entry points are folded into their base calls
+    for s in ("gstex_raster_fwd_zero", "gstex_raster_bwd_zero", "gstex_raster_setup_bwd_aabb",
+              "gstex_bin_sort_ordered", "gstex_bin_sort_capped", "gstex_scan_offsets_guarded", "gstex_adam_step_ex",
+              "gstex_adam_step_scaled", "gstex_adam_step_guarded"):
+        assert s not in syms and not hasattr(lib, s), f"{s} was removed in ABI 19 but is still exported"
 
 
 def test_abi_version(lib):
-    assert lib.gstex_abi_version() == _lib.ABI_VERSION == 18
+    assert lib.gstex_abi_version() == _lib.ABI_VERSION == 19
 
 
 def test_workspace_size_queries(lib):
@@ -59,23 +64,58 @@ def _status(lib, name, *args):
 
 
 def test_bin_sort_rejects_non16_block(lib):
-    rc, msg = _status(lib, "gstex_bin_sort", 10, 10, None, None, None, None, None, 32, 32, 8, None, None, None, None,
-                      0, None)
+    rc, msg = _status(lib, "gstex_bin_sort", 10, 10, None, None, None, None, 32, 32, 8, None, None, None, None, 0,
+                      None, 0, None)
     assert rc == 1 and "block_width must be 16" in msg
+
+
+def test_bin_sort_rejects_bad_flags(lib):
+    # GSTEX_BIN_CAPPED without a tile_order, and flag bits the ABI does not define
+    rc, msg = _status(lib, "gstex_bin_sort", 10, 10, None, None, None, None, 32, 32, 16, None, None, None, None,
+                      _lib.BIN_CAPPED, None, 0, None)
+    assert rc == 1 and "null tile_order" in msg
+    rc, msg = _status(lib, "gstex_bin_sort", 10, 10, None, None, None, None, 32, 32, 16, None, None, None, None,
+                      1 << 2, None, 0, None)
+    assert rc == 1 and "unknown flags" in msg
+
+
+def test_scan_rejects_negative_guard_capacity(lib):
+    guard = _lib.GstexPairGuard(-1, None, None, 1)
+    rc, msg = _status(lib, "gstex_scan_offsets", 0, None, None, None, 0, ctypes.byref(guard), None)
+    assert rc == 1 and "capacity < 0" in msg
+
+
+def _fwd_args(cam, channels=3, settings=0, **kw):
+    return _lib.GstexRasterFwdArgs(scene=_lib.GstexRasterScene(cam=cam, channels=channels, settings=settings,
+                                                               tex_scale=1.0), **kw)
+
+
+def _bwd_args(cam, channels=3, settings=0, **kw):
+    return _lib.GstexRasterBwdArgs(scene=_lib.GstexRasterScene(cam=cam, channels=channels, settings=settings,
+                                                               tex_scale=1.0), **kw)
 
 
 def test_raster_rejects_bad_channels_and_settings(lib):
     cam = _cam()
-    rc, msg = _status(lib, "gstex_raster_fwd", ctypes.byref(cam), 9, 0, None, None, None, None, None, None, None, 0, 1.0,
-                      0.0, None, None, None, None, None, None, None, 0, None, None)
+    rc, msg = _status(lib, "gstex_raster_fwd", ctypes.byref(_fwd_args(cam, channels=9)), None)
     assert rc == 1 and "channels" in msg
-    rc, msg = _status(lib, "gstex_raster_fwd", ctypes.byref(cam), 3, 1 << 2, None, None, None, None, None, None, None, 0,
-                      1.0, 0.0, None, None, None, None, None, None, None, 0, None, None)
+    rc, msg = _status(lib, "gstex_raster_fwd", ctypes.byref(_fwd_args(cam, settings=1 << 2)), None)
     assert rc == 3 and "unsupported settings" in msg
-    bad = _cam(block=8)
-    rc, msg = _status(lib, "gstex_raster_bwd", ctypes.byref(bad), 3, 0, None, None, None, None, None, None, None, 0,
-                      1.0, 0.0, None, None, None, None, None, None, None, 0, None, None, None, None, None)
+    rc, msg = _status(lib, "gstex_raster_bwd", ctypes.byref(_bwd_args(_cam(block=8))), None)
     assert rc == 1 and "block_width" in msg
+
+
+def test_raster_rejects_bad_zero_buffers(lib):
+    cam = _cam()
+    buf = ctypes.addressof((ctypes.c_float * 4)())  # (compared and null-checked only: rejected before any launch)
+    rc, msg = _status(lib, "gstex_raster_bwd", ctypes.byref(_bwd_args(cam, v_texture=buf, zero_buf=buf,
+                                                                      zero_floats=4)), None)
+    assert rc == 1 and "zero_buf" in msg and "must not be the gradient accumulated" in msg
+    rc, msg = _status(lib, "gstex_raster_bwd", ctypes.byref(_bwd_args(cam, zero_buf=buf, zero_floats=-1)), None)
+    assert rc == 1 and "invalid zero_buf / zero_floats" in msg
+    for kw in (dict(zero_buf=buf, zero_floats=-1), dict(zero_buf2=buf, zero_floats2=-1), dict(zero_floats=4)):
+        rc, msg = _status(lib, "gstex_raster_fwd", ctypes.byref(_fwd_args(cam, **kw)), None)
+        assert rc == 1 and "invalid zero_buf / zero_floats" in msg, kw
 
 
 def test_raster_aux_bytes(lib):
@@ -128,13 +168,19 @@ def test_python_wrappers_refuse_cpu_tensors():
 def test_adam_rejects_bad_tables(lib):
     from gstex_amd import _lib
 
-    rc, msg = _status(lib, "gstex_adam_step", 17, None, 0.9, 0.999, 1e-15, None)
+    plain = (0, 1.0, None, None)  # flags, grad_scale, skip, stream
+    rc, msg = _status(lib, "gstex_adam_step", 17, None, 0.9, 0.999, 1e-15, *plain)
     assert rc == 1 and "n_tensors" in msg
     t = (_lib.GstexAdamTensor * 1)(_lib.GstexAdamTensor(None, None, None, None, 10, 1e-3, 1.0))
-    rc, msg = _status(lib, "gstex_adam_step", 1, t, 0.9, 0.999, 1e-15, None)
+    rc, msg = _status(lib, "gstex_adam_step", 1, t, 0.9, 0.999, 1e-15, *plain)
     assert rc == 1 and "null pointer" in msg
     t = (_lib.GstexAdamTensor * 1)(_lib.GstexAdamTensor(None, None, None, None, 0, 1e-3, 1.0))
-    assert _status(lib, "gstex_adam_step", 1, t, 0.9, 0.999, 1e-15, None)[0] == 0  # empty: no launch
+    assert _status(lib, "gstex_adam_step", 1, t, 0.9, 0.999, 1e-15, *plain)[0] == 0  # empty: no launch
+    rc, msg = _status(lib, "gstex_adam_step", 1, t, 0.9, 0.999, 1e-15, 1 << 1, 1.0, None, None)
+    assert rc == 1 and "unknown flags" in msg
+    for scale in (0.0, 1.5, float("nan")):
+        rc, msg = _status(lib, "gstex_adam_step", 1, t, 0.9, 0.999, 1e-15, 0, scale, None, None)
+        assert rc == 1 and "grad_scale must be in (0, 1]" in msg, scale
 
 
 def test_loss_rejects_small_images_and_channels(lib):
@@ -171,7 +217,10 @@ def test_struct_layouts_match_header(tmp_path):
     structs = {"gstex_camera": _lib.GstexCamera, "gstex_pair_guard": _lib.GstexPairGuard,
                "gstex_adam_tensor": _lib.GstexAdamTensor,
                "gstex_train_prologue_args": _lib.GstexTrainPrologueArgs,
-               "gstex_train_epilogue_args": _lib.GstexTrainEpilogueArgs}
+               "gstex_train_epilogue_args": _lib.GstexTrainEpilogueArgs,
+               "gstex_raster_scene": _lib.GstexRasterScene, "gstex_raster_fwd_args": _lib.GstexRasterFwdArgs,
+               "gstex_raster_bwd_args": _lib.GstexRasterBwdArgs,
+               "gstex_raster_setup_bwd_args": _lib.GstexRasterSetupBwdArgs}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "gstex_hip.h"', "int main(void) {"]
     for cname, cls in structs.items():
         lines.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')

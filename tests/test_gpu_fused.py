@@ -141,7 +141,7 @@ def test_fused_step_with_gradsync_trains_like_per_op(monkeypatch):
 
 def test_epilogue_matches_per_op_entry_points():
     """gstex_train_epilogue (setup bwd + activation bwd + SH rest bwd in one kernel) writes bit-identical gradients to
-    gstex_raster_setup_bwd_aabb -> gstex_activate_bwd / gstex_sh_rest_bwd on the same accumulator rows."""
+    gstex_raster_setup_bwd (fold_aabb) -> gstex_activate_bwd / gstex_sh_rest_bwd on the same accumulator rows."""
     import ctypes
 
     from gstex_amd import _lib, ops
@@ -173,9 +173,12 @@ def test_epilogue_matches_per_op_entry_points():
     P = _lib.ptr
     st = _lib.stream_of(dev)
     a = bufs()
-    _lib.call("gstex_raster_setup_bwd_aabb", n, P(tr.means), P(scl), 1.0, P(qn), P(op), P(umap), P(vmap), P(nth),
-              P(offsets), P(partials), None, 24, -1, cam, P(a["v_means"]), P(a["v_sc"]), P(a["v_qn"]),
-              P(a["v_rgbs"]), P(a["v_op"]), P(a["v_c"]), P(a["v_uv"]), st)
+    sb = _lib.GstexRasterSetupBwdArgs(
+        n=n, glob_scale=1.0, row_floats=24, fold_aabb=1, n_rows=-1, cam=cam, means=P(tr.means), scales=P(scl),
+        quats=P(qn), umap=P(umap), vmap=P(vmap), num_tiles_hit=P(nth), offsets=P(offsets), partials=P(partials),
+        row_flags=None, v_means=P(a["v_means"]), v_scales=P(a["v_sc"]), v_quats=P(a["v_qn"]), v_rgbs=P(a["v_rgbs"]),
+        v_opacities=P(a["v_op"]), v_centers=P(a["v_c"]), v_uv0=P(a["v_uv"]))
+    _lib.call("gstex_raster_setup_bwd", ctypes.byref(sb), st)
     _lib.call("gstex_sh_rest_bwd", n, 3, n_rest, P(vd), P(a["v_rgbs"]), P(a["v_rest"]), st)
     _lib.call("gstex_activate_bwd", n, P(tr.quats), P(tr.scales), P(op), P(a["v_qn"]), P(a["v_sc"]), P(a["v_op"]),
               P(a["v_quats"]), P(a["v_log_scales"]), P(a["v_opac_logits"]), st)

@@ -296,7 +296,7 @@ def test_unit_order(n_units, groups):
 
 @pytest.mark.parametrize("H,W,n", [(80, 96, 400), (64, 64, 0), (2064, 2064, 3000)])  # 16641 tiles: row-major
 def test_bin_sort_ordered_matches_tile_order(H, W, n):
-    """gstex_bin_sort_ordered: the binning as gstex_bin_sort, plus the launch order gstex_tile_order computes
+    """gstex_bin_sort with a tile_order: the binning as without one, plus the launch order gstex_tile_order computes
     from the resulting tile ranges (the forward reuses it instead of ranking the tiles twice)."""
     from gstex_amd import ops
 
@@ -412,14 +412,15 @@ def test_fused_adam_matches_torch_adam():
 
 
 def test_fused_adam_grad_scale_bit_identical():
-    """grad_scale (gstex_adam_step_scaled, the data-parallel 1 / world folded into the update) == scaling the gradient
-    first and stepping unscaled, bit for bit; with zero_grad the gradient is left zeroed."""
+    """grad_scale (gstex_adam_step; the data-parallel 1 / world folded into the update) == scaling the gradient
+    first and stepping unscaled, bit for bit; with zero_grad the gradient is left zeroed.  scale 1.0: zero_grad alone;
+    grid > 0: the launch capped to that many workgroups (GSTEX_ADAM_GRID; 295 chunks here), each looping over chunks."""
     from gstex_amd.optim import FusedAdam
 
     g = torch.Generator().manual_seed(22)
     shapes = [(100_001, 3), (513,), (64, 4)]
     base = [torch.randn(s, generator=g) for s in shapes]
-    for scale in (0.5, 1.0 / 3.0, 0.125):
+    for scale, grid in ((0.5, 0), (1.0 / 3.0, 0), (0.125, 0), (1.0, 0), (1.0, 3), (0.5, 7)):
         a = [torch.nn.Parameter(t.clone().to(DEV)) for t in base]
         b = [torch.nn.Parameter(t.clone().to(DEV)) for t in base]
         opt_a = FusedAdam([{"params": a, "lr": 1e-3}], eps=1e-15)
@@ -429,7 +430,7 @@ def test_fused_adam_grad_scale_bit_identical():
                 gr = torch.randn(pa.shape, generator=g).to(DEV)
                 pa.grad = gr.clone()
                 pb.grad = gr * scale
-            opt_a.step(grad_scale=scale, zero_grad=step == 2)
+            opt_a.step(grad_scale=scale, zero_grad=step == 2, grid=grid)
             opt_b.step()
             for pa, pb in zip(a, b):
                 assert torch.equal(pa.detach(), pb.detach())

@@ -58,7 +58,7 @@ def main():
     nth = run()
     torch.cuda.synchronize()
     ops.set_kernel_timing(True, names={"gstex_bin_sort", "gstex_raster_setup", "gstex_raster_fwd", "gstex_raster_bwd",
-                                      "gstex_raster_setup_bwd", "gstex_raster_setup_bwd_aabb"})
+                                      "gstex_raster_setup_bwd"})
     t0 = time.perf_counter()
     for _ in range(args.iters):
         run()
