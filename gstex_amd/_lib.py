@@ -123,6 +123,14 @@ class GstexRasterSetupBwdArgs(ctypes.Structure):
             "v_means", "v_scales", "v_quats", "v_rgbs", "v_opacities", "v_centers", "v_uv0")]
 
 
+class GstexLossTarget(ctypes.Structure):
+    """gstex_loss_target (added within ABI 19): the dataset image and mask of gstex_loss_target_fwd / _bwd."""
+    _fields_ = [("gt", c_void_p), ("mask", c_void_p), ("gt_dtype", c_int32), ("gt_channels", c_int32),
+                ("mask_dtype", c_int32), ("reserved", c_int32)]
+
+
+GT_F32, GT_U8 = 0, 1  # GSTEX_GT_*
+MASK_F32, MASK_BOOL = 0, 1  # GSTEX_MASK_*
 ADAM_ZERO_GRAD = 1  # GSTEX_ADAM_ZERO_GRAD
 ADAM_GRID_SHIFT = 8  # GSTEX_ADAM_GRID_SHIFT
 BIN_CAPPED = 1  # GSTEX_BIN_CAPPED
@@ -179,6 +187,11 @@ SIGNATURES = {
                                  _P, c_size_t, _P]),
     "gstex_loss_bwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, POINTER(c_float), c_float, _P, _P,
                                  _P, _P, _P, c_size_t, _P]),
+    "gstex_loss_target_workspace_size": (c_size_t, [c_int32, c_int32]),
+    "gstex_loss_target_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, POINTER(GstexLossTarget),
+                                        POINTER(c_float), c_float, _P, _P, _P, _P, c_size_t, _P]),
+    "gstex_loss_target_bwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, POINTER(GstexLossTarget),
+                                        POINTER(c_float), c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
     "gstex_adam_step": (c_int32, [c_int32, POINTER(GstexAdamTensor), c_double, c_double, c_double, c_int32, c_float,
                                   _P, _P]),
     "gstex_train_prologue": (c_int32, [POINTER(GstexTrainPrologueArgs), _P]),

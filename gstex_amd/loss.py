@@ -5,10 +5,15 @@ rasterizer outputs: the background composite and clamp (gstex.py:1204-1205) foll
 ``0.8 * L1 + 0.2 * (1 - SSIM)`` (gstex.py:1301-1322, pytorch_msssim SSIM, 11-tap sigma-1.5 window,
 valid filtering).  One forward launch (+ a one-workgroup reduction) and one backward launch replace
 the ~40 elementwise kernels and four GEMMs the same expression costs in eager PyTorch.
+
+``image_loss(img, tex, alpha, background, image, mask=None)`` is the same loss on the image a dataset delivers
+(``gstex_loss_target_fwd`` / ``_bwd``): a uint8 or float32 target with 3 or 4 channels, an optional mask, and the
+step's MSE (for PSNR) from the same launch; ``image_loss_eager`` restates it with torch ops.
 """
 from __future__ import annotations
 
 import ctypes
+from dataclasses import dataclass
 
 import torch
 
@@ -92,6 +97,158 @@ class _PhotometricLoss(torch.autograd.Function):
 def photometric_loss(img, tex, alpha, background, gt, ssim_lambda: float = 0.2):
     """Returns (loss, rgb): loss is the differentiable 0-dim training loss, rgb the composited image."""
     return _PhotometricLoss.apply(img, tex, alpha, background, gt, ssim_lambda)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the loss on the image a dataset delivers: uint8 / RGBA targets and masks (gstex.py:1238-1260, 1277-1303)
+# ---------------------------------------------------------------------------------------------------------------
+@dataclass
+class ImageLoss:
+    """What image_loss / image_loss_eager return.  loss: the differentiable 0-dim training loss; rgb: the composited
+    (unmasked) render, outputs["rgb"]; gt: the composited unmasked target (H, W, 3); terms: four floats
+    [loss, L1, SSIM, MSE] on the device (PSNR = -10 log10(MSE), get_metrics_dict)."""
+    loss: torch.Tensor
+    rgb: torch.Tensor
+    gt: torch.Tensor
+    terms: torch.Tensor
+
+    def psnr(self) -> torch.Tensor:
+        return -10.0 * torch.log10(self.terms[3])
+
+
+def _check_target(name, alpha, image, mask):
+    """The dataset image and mask (dtypes and shapes), refused in words before any HIP call.  Returns the mask as
+    (H, W) (or None)."""
+    H, W = alpha.shape
+    if image.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"{name}: image must be float32 or uint8 (got {image.dtype})")
+    if image.dim() != 3 or tuple(image.shape[:2]) != (H, W) or image.shape[2] not in (3, 4):
+        raise ValueError(f"{name}: image must have shape ({H}, {W}, 3) or ({H}, {W}, 4) (got {tuple(image.shape)})")
+    if mask is not None:
+        if mask.dtype == torch.uint8:
+            raise ValueError(f"{name}: a uint8 mask is ambiguous (0/1 or 0/255?): pass bool or float32")
+        if mask.dtype not in (torch.bool, torch.float32):
+            raise ValueError(f"{name}: mask must be bool or float32 (got {mask.dtype})")
+        if tuple(mask.shape) not in ((H, W), (H, W, 1)):
+            raise ValueError(f"{name}: mask must have shape ({H}, {W}) or ({H}, {W}, 1) (got {tuple(mask.shape)})")
+        mask = mask.reshape(H, W)
+    return mask
+
+
+def _check_image(img, tex, alpha, background, image, mask):
+    """Shapes and dtypes first, then the window, then the device: each refusal names what is wrong with the call."""
+    if alpha.dim() != 2:
+        raise ValueError("image_loss: alpha must be a CUDA fp32 tensor of shape (H, W)")
+    H, W = alpha.shape
+    for name, t, shape in (("img", img, (H, W, 3)), ("alpha", alpha, (H, W)), ("background", background, (3,))):
+        if tuple(t.shape) != shape or t.dtype != torch.float32:
+            raise ValueError(f"image_loss: {name} must be a CUDA fp32 tensor of shape {shape}")
+    if tex.dim() != 3 or tuple(tex.shape[:2]) != (H, W) or not 3 <= tex.shape[2] <= 8 or tex.dtype != torch.float32:
+        raise ValueError("image_loss: tex must be CUDA fp32 (H, W, C) with 3 <= C <= 8")
+    mask = _check_target("image_loss", alpha, image, mask)
+    if H <= 10 or W <= 10:
+        raise ValueError("image_loss: the image must be larger than the 11-tap SSIM window")
+    for name, t in (("img", img), ("tex", tex), ("alpha", alpha), ("background", background), ("image", image),
+                    ("mask", mask)):
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"image_loss: {name} must be a CUDA tensor")
+    return mask
+
+
+def _aligned(t: torch.Tensor, nbytes: int) -> torch.Tensor:
+    """t, or a fresh copy when its storage offset breaks the kernels' pixel load (an RGBA pixel is one load)."""
+    return t if t.data_ptr() % nbytes == 0 else t.clone()
+
+
+def _loss_target(image, mask) -> _lib.GstexLossTarget:
+    return _lib.GstexLossTarget(
+        ptr(image), ptr(mask), _lib.GT_U8 if image.dtype == torch.uint8 else _lib.GT_F32, int(image.shape[2]),
+        _lib.MASK_BOOL if mask is not None and mask.dtype == torch.bool else _lib.MASK_F32, 0)
+
+
+class _ImageLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, tex, alpha, background, image, mask, ssim_lambda):
+        mask = _check_image(img, tex, alpha, background, image, mask)
+        img, tex, alpha, background = (t.detach().contiguous() for t in (img, tex, alpha, background))
+        image = _aligned(image.detach().contiguous(), 16)
+        if mask is not None:
+            mask = _aligned(mask.detach().contiguous(), 4)
+        H, W = alpha.shape
+        C = tex.shape[2]
+        cwin = _cwin()
+        dev = img.device
+        ws = torch.empty((int(_lib.load().gstex_loss_target_workspace_size(H, W)),), device=dev, dtype=torch.uint8)
+        terms = torch.empty((4,), device=dev, dtype=torch.float32)
+        rgb = torch.empty((H, W, 3), device=dev, dtype=torch.float32)
+        gt = torch.empty((H, W, 3), device=dev, dtype=torch.float32)
+        target = _loss_target(image, mask)
+        call("gstex_loss_target_fwd", H, W, C, ptr(img), ptr(tex), ptr(alpha), ptr(background), ctypes.byref(target),
+             cwin, float(ssim_lambda), ptr(rgb), ptr(gt), ptr(terms), ptr(ws), ws.numel(), _lib.stream_of(dev))
+        saved = (img, tex, alpha, background, image, ws) + ((mask,) if mask is not None else ())
+        ctx.save_for_backward(*saved)
+        ctx.ssim_lambda = float(ssim_lambda)
+        ctx.mark_non_differentiable(rgb, gt, terms)
+        ctx.set_materialize_grads(False)
+        return terms[0], rgb, gt, terms
+
+    @staticmethod
+    def backward(ctx, g_loss, g_rgb, g_gt, g_terms):
+        if g_loss is None:
+            return (None,) * 7
+        img, tex, alpha, background, image, ws, *rest = ctx.saved_tensors
+        mask = rest[0] if rest else None
+        H, W = alpha.shape
+        C = tex.shape[2]
+        d_img = torch.empty_like(img)
+        d_tex = torch.empty_like(tex)
+        d_alpha = torch.empty_like(alpha)
+        g = g_loss.detach().to(torch.float32).contiguous()
+        target = _loss_target(image, mask)
+        call("gstex_loss_target_bwd", H, W, C, ptr(img), ptr(tex), ptr(alpha), ptr(background), ctypes.byref(target),
+             _cwin(), ctx.ssim_lambda, g.data_ptr(), ptr(d_img), ptr(d_tex), ptr(d_alpha), ptr(ws), ws.numel(),
+             _lib.stream_of(img.device))
+        return d_img, d_tex, d_alpha, None, None, None, None
+
+
+def image_loss(img, tex, alpha, background, image, mask=None, ssim_lambda: float = 0.2) -> ImageLoss:
+    """The training loss of get_loss_dict on the raw rasterizer outputs and the image a dataset delivers, in one
+    forward and one backward launch: `image` is float32 or uint8 (v / 255, get_gt_img), (H, W, 3) or (H, W, 4)
+    (straight alpha, composited on `background` as composite_with_background does); `mask` is bool or float32,
+    (H, W) or (H, W, 1): L1 and SSIM see gt * mask and rgb * mask (gstex.py:1294-1299), the MSE does not.
+    `background` is read on the device by the kernels (no host synchronisation)."""
+    loss, rgb, gt, terms = _ImageLoss.apply(img, tex, alpha, background, image, mask, ssim_lambda)
+    return ImageLoss(loss, rgb, gt, terms)
+
+
+def image_loss_eager(rgb, background, image, mask=None, ssim_lambda: float = 0.2) -> ImageLoss:
+    """image_loss with torch ops on the composited render `rgb`, restating gstex.py:1244-1245, 1256-1258 and
+    1294-1303 (runs on any device; the trainer's fused_loss=False path and the tests' reference)."""
+    from .model import ssim  # (model imports this module)
+
+    if rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise ValueError("image_loss_eager: rgb must have shape (H, W, 3)")
+    mask = _check_target("image_loss_eager", rgb[..., 0], image, mask)
+    if image.dtype == torch.uint8:
+        # a tensor divisor: by a Python scalar torch's device kernel multiplies by the rounded reciprocal instead,
+        # which is not the division the CPU data path (and the fused kernel) performs
+        image = image.float() / torch.full((), 255.0, device=image.device)
+    if image.shape[2] == 4:
+        a = image[..., -1].unsqueeze(-1).repeat((1, 1, 3))
+        gt = a * image[..., :3] + (1 - a) * background
+    else:
+        gt = image
+    mse = torch.mean((rgb.detach() - gt) ** 2)
+    x, y = gt, rgb
+    if mask is not None:
+        m = mask[..., None]
+        x = x * m
+        y = y * m
+    l1 = torch.abs(x - y).mean()
+    sim = ssim(x.permute(2, 0, 1)[None, ...], y.permute(2, 0, 1)[None, ...])
+    loss = (1 - ssim_lambda) * l1 + ssim_lambda * (1 - sim)
+    terms = torch.stack([loss.detach(), l1.detach(), sim.detach(), mse])
+    return ImageLoss(loss, rgb.detach(), gt, terms)
 
 
 # ---------------------------------------------------------------------------------------------------------------

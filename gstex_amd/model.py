@@ -11,6 +11,9 @@ Reproduces the parts of the reference's GStexModel that sit either side of the h
   * background composite             gstex.py:1204-1205
   * loss 0.8 L1 + 0.2 (1 - SSIM)     gstex.py:1301-1322 (pytorch_msssim SSIM semantics; fused HIP
                                      kernels in gstex_amd.loss, eager torch path kept for reference)
+  * the batch image as delivered     gstex.py:1238-1260, 1294-1299 (uint8 / RGBA targets on the step's background,
+                                     masks, the step's MSE: inside the same loss kernels, gstex_amd.loss.image_loss)
+  * background_color                 gstex.py:178, 1012-1020 ("random": a fresh colour per step, drawn on the device)
   * per-group Adam, eps 1e-15        gstex_configs.py:207-244, engine/optimizers.py:158-171
                                      (one fused HIP launch, gstex_amd.optim.FusedAdam)
 The rechart every 100 steps (gstex.py:890-914) is provided by `recharge()`.
@@ -26,7 +29,8 @@ import torch.nn.functional as F
 
 from . import ops
 from .activations import activate, sh_rest
-from .loss import depth_to_normal, gaussian_window, geometry_loss, photometric_loss, scheduled
+from .loss import (depth_to_normal, gaussian_window, geometry_loss, image_loss, image_loss_eager, photometric_loss,
+                   scheduled)
 from .optim import FusedAdam
 from .charts import SH2RGB, build_charts, get_uv_mapping, texture_dims_to_query
 from .scene import Scene, View
@@ -42,6 +46,9 @@ LRS = {
     "texture_dc": 1e-3,
 }
 DEFAULT_SETTINGS = (1 << 9) | (1 << 10)
+BACKGROUNDS = {"white": (1.0, 1.0, 1.0), "black": (0.0, 0.0, 0.0)}  # background_color names (gstex.py:1012-1020)
+# the fixed colour a background="random" model renders on outside training (gstex.py:355-358)
+VIEWER_BACKGROUND = (0.1490, 0.1647, 0.2157)
 SH_C0 = 0.28209479177387814  # SH2RGB(x) = SH_C0 * x + 0.5 (gstex.py:94-99)
 
 
@@ -97,6 +104,7 @@ def ssim(x: torch.Tensor, y: torch.Tensor, data_range=1.0, win_size=11, sigma=1.
 class StepOutput:
     loss: torch.Tensor
     rgb: torch.Tensor
+    terms: torch.Tensor | None = None  # [main loss, L1, SSIM, MSE] of a step through image_loss (else None)
 
 
 class GStexTrainer:
@@ -107,7 +115,7 @@ class GStexTrainer:
                  fused_loss: bool = True, fused_activations: bool = True, geometry_outputs: bool = False,
                  sh_degree_interval: int = 1000, fix_init: bool = False, start_step: int = 0,
                  defer_texture: bool = False, lambda_normal=0.0, lambda_reg=0.0, use_normal_loss: bool = False,
-                 pair_capacity: bool | None = None, fused_step: bool | None = None):
+                 pair_capacity: bool | None = None, fused_step: bool | None = None, background_seed: int = 0):
         self.device = torch.device(device)
         d = self.device
         P = lambda t: torch.nn.Parameter(t.detach().to(d).contiguous())  # noqa: E731
@@ -137,7 +145,21 @@ class GStexTrainer:
         self.sh_degree = sh_degree
         self.settings = settings
         self.pixel_num = pixel_num if pixel_num is not None else float(scene.texture.shape[0])
+        # background: a colour, "white", "black", or "random" (gstex.py:178, 1012-1020): a fresh uniform colour per
+        # training step, drawn on the device into this same tensor (refresh_background), which feeds the render's
+        # composite, the loss and an RGBA target's composite alike.  background_seed (not in the reference, which
+        # draws from the global generator) seeds the trainer's own device generator.
+        self.random_background = isinstance(background, str) and background == "random"
+        if isinstance(background, str):
+            if not self.random_background and background not in BACKGROUNDS:
+                raise ValueError(f'background must be a colour, "white", "black" or "random" (got {background!r})')
+            background = BACKGROUNDS.get(background, VIEWER_BACKGROUND)
         self.background = torch.tensor(background, dtype=torch.float32, device=d)
+        self._eval_background = self.background.clone() if self.random_background else self.background
+        self._background_gen = None
+        if self.random_background:
+            self._background_gen = torch.Generator(device=d)
+            self._background_gen.manual_seed(int(background_seed))
         # the raster's own background is zero (the composite adds the real one, gstex.py:1204): one cached tensor
         self._bg_zero = torch.zeros_like(self.background)
         self._one = torch.ones((), dtype=torch.float32, device=d)
@@ -454,7 +476,7 @@ class GStexTrainer:
             inv = torch.where(n2 > 0, 1.0 / torch.sqrt(n2), torch.zeros_like(n2))
             n_edit, n_unit = None, normal * inv[..., None]
         zeros3 = torch.zeros_like(img)  # texture channels 3..5 of every call
-        bg = self.background[None, None, :]
+        bg = self._eval_background[None, None, :]  # (the trainer's background; the viewer colour under "random")
         rgb = torch.clamp(img + tex[..., 0:3] + (1 - alpha[..., None]) * bg, 0.0, 1.0)
         edit_tex_img = n_edit[..., :3] if n_edit is not None else zeros3
         return dict(rgb=rgb, depth=depth, alpha=alpha, normal=normal,
@@ -472,12 +494,31 @@ class GStexTrainer:
         """The SH degree ramp of the reference: min(step // sh_degree_interval, sh_degree) (gstex.py:1103)."""
         return min(self.step // self.sh_degree_interval, self.sh_degree)
 
-    def forward_backward(self, view: View, gt: torch.Tensor) -> StepOutput:
+    def refresh_background(self) -> torch.Tensor:
+        """The step's background: under background="random" a fresh uniform colour written into self.background on the
+        device (no host read-back); forward_backward calls it once per step, before the render."""
+        if self.random_background:
+            self.background.uniform_(0.0, 1.0, generator=self._background_gen)
+        return self.background
+
+    def forward_backward(self, view: View, gt: torch.Tensor, mask: torch.Tensor | None = None) -> StepOutput:
+        """One training step's loss and gradients.  gt: the target as the dataset delivers it -- float32 or uint8,
+        (H, W, 3), or (H, W, 4) with straight alpha (composited on the step's background); mask: bool or float32,
+        (H, W) or (H, W, 1), applied to both images before L1 and SSIM (gstex.py:1294-1299)."""
         lam_n, lam_r = scheduled(self.lambda_normal, self.step), scheduled(self.lambda_reg, self.step)
         geo = lam_n != 0.0 or lam_r != 0.0
+        self.refresh_background()
         out = self.render(view, sh_degree_now=self.sh_degree_now(), composite=not self.fused_loss,
                           geometry=True if geo else None)
-        if self.fused_loss:  # composite + clamp + L1/SSIM in one HIP launch pair (gstex_amd.loss)
+        terms = None
+        if mask is not None or gt.dtype != torch.float32 or gt.shape[-1] != 3:
+            # a dataset target: conversion, alpha composite and mask inside the loss kernels (gstex_amd.loss)
+            if self.fused_loss:
+                res = image_loss(out["img"], out["tex"], out["alpha"], self.background, gt, mask)
+            else:
+                res = image_loss_eager(out["rgb"], self.background, gt, mask)
+            loss, rgb, terms = res.loss, res.rgb, res.terms
+        elif self.fused_loss:  # composite + clamp + L1/SSIM in one HIP launch pair (gstex_amd.loss)
             loss, rgb = photometric_loss(out["img"], out["tex"], out["alpha"], self.background, gt.contiguous())
         else:
             rgb = out["rgb"]
@@ -488,7 +529,7 @@ class GStexTrainer:
                    if self.use_normal_loss else out["normal"])
             loss = loss + geometry_loss(out["alpha"], out["normal"], est, out["reg"], lam_n, lam_r)
         loss.backward(self._one)  # (a cached seed: no per-step fill launch for the implicit ones_like)
-        return StepOutput(loss.detach(), rgb.detach())
+        return StepOutput(loss.detach(), rgb.detach(), terms)
 
     def optimizer_step(self, sync=None):
         """The Adam step.  With a gstex_amd.dist.GradSync `sync` (data-parallel training) the gradient exchange is part

@@ -45,7 +45,9 @@ extern "C" {
  * fold_aabb (was _aabb), gstex_bin_sort takes tile_order and flags (was _ordered, _capped), gstex_scan_offsets takes a
  * nullable guard (was _guarded), gstex_adam_step takes flags, grad_scale and skip (was _ex, _scaled, _guarded).
  * ABI 18 (round 6): the hipGraph step support of ABI 16 (event-record nodes, gstex_adam_step_scheduled) and the
- * split-backward settings bit of ABI 15 are removed (measured slower). */
+ * split-backward settings bit of ABI 15 are removed (measured slower).
+ * The number counts incompatible changes: an addition that leaves every existing symbol's signature and meaning alone
+ * keeps it, and is marked "added within ABI 19 (additive)" where it is declared (gstex_loss_target_*). */
 #define GSTEX_ABI_VERSION 19
 
 /* Per-record layout of the splat table written by gstex_raster_setup (floats). */
@@ -391,6 +393,41 @@ int gstex_loss_bwd(int32_t H, int32_t W, int32_t C, const float* img, const floa
                    const float* background, const float* gt, const float* window, float ssim_lambda,
                    const float* grad_loss, float* d_img, float* d_tex, float* d_alpha, void* workspace,
                    size_t workspace_bytes, void* stream);
+
+/* The same loss on the target a dataset delivers -- added within ABI 19 (additive).
+ * get_gt_img (gstex.py:1238-1247), composite_with_background (:1249-1260), the mask branch of get_loss_dict
+ * (:1294-1299) and the MSE of get_metrics_dict's PSNR (:1262-1275) folded into the loss kernels' staging loop.
+ * Each line is one individually rounded fp32 operation:
+ *   g_c  = the stored value (F32) or (float)v / 255.0f (U8); with four channels a = channel 3, converted alike
+ *   gt_c = g_c (3 channels), or a * g_c + (1 - a) * background_c (4: two rounded products, then the sum)
+ *   rgb_c as gstex_loss_fwd (rgb_out is the unmasked clamped image)
+ *   m    = the mask value (F32), v != 0 ? 1 : 0 (BOOL), or 1 without a mask;  X_c = gt_c * m,  Y_c = rgb_c * m
+ *   L1 = mean|X - Y|, SSIM = SSIM(X, Y) as gstex_loss_fwd; MSE = mean (rgb_c - gt_c)^2, unmasked
+ *   terms_out (device float[4]) = {(1 - ssim_lambda) L1 + ssim_lambda (1 - SSIM), L1, SSIM, MSE}
+ *   (PSNR = -10 log10(MSE) is the caller's); gt_out (nullable, H*W*3) = gt.
+ * Backward: dL/drgb_c = m * dL/dY_c, gated by the clamp; d_img, d_tex, d_alpha as gstex_loss_bwd.
+ * The target is a HOST struct of DEVICE pointers.  An RGBA pixel is read in one load: gt must be 4-byte (U8) or
+ * 16-byte (F32) aligned.  The workspace is gstex_loss_target_workspace_size bytes (0 when H or W <= 10), shared by
+ * the forward and its backward. */
+enum { GSTEX_GT_F32 = 0, GSTEX_GT_U8 = 1 };       /* U8: value = (float)v / 255.0f (a true division) */
+enum { GSTEX_MASK_F32 = 0, GSTEX_MASK_BOOL = 1 }; /* BOOL: one byte per pixel, m = v != 0 ? 1.0f : 0.0f */
+typedef struct gstex_loss_target {
+    const void* gt;      /* H*W*gt_channels, row-major, channel last */
+    const void* mask;    /* nullable = no mask; H*W */
+    int32_t gt_dtype;    /* GSTEX_GT_* */
+    int32_t gt_channels; /* 3, or 4: straight alpha in channel 3, composited on `background` */
+    int32_t mask_dtype;  /* GSTEX_MASK_* (ignored when mask is NULL) */
+    int32_t reserved;    /* must be 0 */
+} gstex_loss_target;
+size_t gstex_loss_target_workspace_size(int32_t H, int32_t W);
+int gstex_loss_target_fwd(int32_t H, int32_t W, int32_t C, const float* img, const float* tex, const float* alpha,
+                          const float* background, const gstex_loss_target* target, const float* window,
+                          float ssim_lambda, float* rgb_out, float* gt_out, float* terms_out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int gstex_loss_target_bwd(int32_t H, int32_t W, int32_t C, const float* img, const float* tex, const float* alpha,
+                          const float* background, const gstex_loss_target* target, const float* window,
+                          float ssim_lambda, const float* grad_loss, float* d_img, float* d_tex, float* d_alpha,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- optimizer (train-step support) ----------------------------------- */
 /* One launch of torch.optim.Adam (no weight decay, no amsgrad) over up to GSTEX_ADAM_MAX_TENSORS
