@@ -192,6 +192,9 @@ SIGNATURES = {
                                         POINTER(c_float), c_float, _P, _P, _P, _P, c_size_t, _P]),
     "gstex_loss_target_bwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, POINTER(GstexLossTarget),
                                         POINTER(c_float), c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gstex_eval_metrics_workspace_size": (c_size_t, [c_int32, c_int32]),
+    "gstex_eval_metrics": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, POINTER(GstexLossTarget),
+                                     POINTER(c_float), _P, _P, _P, _P, _P, c_size_t, _P]),
     "gstex_adam_step": (c_int32, [c_int32, POINTER(GstexAdamTensor), c_double, c_double, c_double, c_int32, c_float,
                                   _P, _P]),
     "gstex_train_prologue": (c_int32, [POINTER(GstexTrainPrologueArgs), _P]),

@@ -22,6 +22,11 @@
 //                                       uint8 -> v / 255, RGBA -> a * g + (1 - a) * bg and the mask multiply happen in
 //                                       the staging loop, once per staged pixel.  gstex_loss_fwd / _bwd are the trivial
 //                                       instantiation (fp32, 3 channels, no mask, no MSE partial): same arithmetic.
+//
+//   gstex_eval_metrics               <- the evaluation protocol of get_image_metrics_and_images (gstex.py:1337-1403) on
+//                                       one view: the render quantised to uint8 (:1379-1381) in the staging loop, PSNR
+//                                       and SSIM against the composited target.  A forward-only sibling of the loss
+//                                       forward (metrics_fwd_kernel, at the end of this file): no gmaps, no mask, no L1.
 #include "gstex_common.h"
 #include "gstex_error.h"
 
@@ -681,3 +686,198 @@ extern "C" int gstex_loss_target_bwd(int32_t H, int32_t W, int32_t C, const floa
     return launch_status("gstex_loss_target_bwd");
 }
 
+// ---- evaluation metrics (uint8-quantised PSNR / SSIM, forward only) ----------------------------------------------
+namespace {
+
+constexpr int kMetricParts = 3;  // per workgroup: {sum s, sum (y - gt)^2, sum (rgb - gt)^2}
+
+// The loss forward's tiling (one workgroup per 16x16 tile and channel, XCD-aware order) with the reference's uint8
+// quantisation of the render in the staging loop: Y = (float)(uint8)(255 rgb) * (1 / 255), X = gt.  No gmaps and no
+// L1; the quantised bytes, the unquantised render and the composited target are optional outputs.  The three channels
+// of a pixel belong to three workgroups, so the rgb_u8_out stores are single bytes three apart.
+template <int DT, int CH>
+__global__ __launch_bounds__(256) void metrics_fwd_kernel(int H, int W, int C, const float* __restrict__ img,
+                                                          const float* __restrict__ tex,
+                                                          const float* __restrict__ alpha,
+                                                          const float* __restrict__ bg, GtPtr<DT> __restrict__ gt,
+                                                          Win win, float* __restrict__ rgb_out,
+                                                          unsigned char* __restrict__ rgb_u8_out,
+                                                          float* __restrict__ gt_out, float* __restrict__ part) {
+    __shared__ float s_x[kReg][kReg + 1], s_y[kReg][kReg + 1];
+    __shared__ float s_h[5][kReg][kLT + 1];
+    __shared__ float s_red[kMetricParts][4];
+    const LossTile lt = loss_tile();
+    const int c = lt.c;
+    const int x0 = lt.bx * kLT, y0 = lt.by * kLT;
+    const int tid = threadIdx.x;
+    const int Hv = H - kHalo, Wv = W - kHalo;
+    float mse = 0.f, mse_raw = 0.f;
+    for (int i = tid; i < kReg * kReg; i += 256) {
+        const int ry = i / kReg, rx = i % kReg;
+        const int y = y0 + ry, x = x0 + rx;
+        float xv = 0.f, yv = 0.f;
+        if (y < H && x < W) {
+            const size_t pix = (size_t)y * W + x;
+            float pre;
+            const float rgbv = composite(img, tex, alpha, bg, C, pix, c, pre);
+            xv = gt_channel<DT, CH>(gt, bg, pix, c);
+            // (255.0 * rgb).to(uint8).to(float32) / 255.0 (gstex.py:1380-1381): the conversion truncates, and the
+            // device divides by a scalar as a multiplication by its rounded reciprocal
+            const float scaled = 255.0f * rgbv;
+            const unsigned char q = (unsigned char)scaled;
+            yv = (float)q * (1.0f / 255.0f);
+            if (rx < kLT && ry < kLT) {  // each pixel's outputs and MSE terms belong to the tile whose core holds it
+                const float d = yv - xv;
+                mse += d * d;
+                const float dr = rgbv - xv;  // unquantised, as get_metrics_dict computes it
+                mse_raw += dr * dr;
+                if (rgb_out) rgb_out[3 * pix + c] = rgbv;
+                if (rgb_u8_out) rgb_u8_out[3 * pix + c] = q;
+                if (gt_out) gt_out[3 * pix + c] = xv;
+            }
+        }
+        s_x[ry][rx] = xv;
+        s_y[ry][rx] = yv;
+    }
+    __syncthreads();
+    // rows, then columns: the loss forward's filters (fused multiply-adds: SSIM is compared with a tolerance)
+    for (int i = tid; i < kReg * kLT; i += 256) {
+#pragma clang fp contract(fast)
+        const int ry = i / kLT, cx = i % kLT;
+        float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
+#pragma unroll
+        for (int k = 0; k < kWin; ++k) {
+            const float xv = s_x[ry][cx + k], yv = s_y[ry][cx + k];
+            a += win.w[k] * xv;
+            b += win.w[k] * yv;
+            aa += win.w[k] * (xv * xv);
+            bb += win.w[k] * (yv * yv);
+            ab += win.w[k] * (xv * yv);
+        }
+        s_h[0][ry][cx] = a;
+        s_h[1][ry][cx] = b;
+        s_h[2][ry][cx] = aa;
+        s_h[3][ry][cx] = bb;
+        s_h[4][ry][cx] = ab;
+    }
+    __syncthreads();
+    const int cy = tid >> 4, cx = tid & 15;
+    const int py = y0 + cy, px = x0 + cx;
+    float ssum = 0.f;
+    if (py < Hv && px < Wv) {
+#pragma clang fp contract(fast)
+        float q[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < kWin; ++k)
+#pragma unroll
+            for (int m = 0; m < 5; ++m) q[m] += win.w[k] * s_h[m][cy + k][cx];
+        const float mu1 = q[0], mu2 = q[1];
+        const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
+        const float s11 = q[2] - mu1_sq, s22 = q[3] - mu2_sq, s12 = q[4] - mu1_mu2;
+        const float A = 2.0f * mu1_mu2 + kC1, B = 2.0f * s12 + kC2;
+        const float Cc = mu1_sq + mu2_sq + kC1, D = s11 + s22 + kC2;
+        ssum = (A / Cc) * (B / D);
+    }
+    // workgroup sums (fixed order: wave reduce, then the 4 waves in order)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        ssum += __shfl_xor(ssum, off, 64);
+        mse += __shfl_xor(mse, off, 64);
+        mse_raw += __shfl_xor(mse_raw, off, 64);
+    }
+    if ((tid & 63) == 0) {
+        s_red[0][tid >> 6] = ssum;
+        s_red[1][tid >> 6] = mse;
+        s_red[2][tid >> 6] = mse_raw;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int b = (lt.c * gridDim.y + lt.by) * gridDim.x + lt.bx;  // tile index: fixed reduction order
+#pragma unroll
+        for (int m = 0; m < kMetricParts; ++m)
+            part[kMetricParts * b + m] = ((s_red[m][0] + s_red[m][1]) + s_red[m][2]) + s_red[m][3];
+    }
+}
+
+// metrics = {PSNR, SSIM, MSE, MSE_raw}; PSNR = -10 log10(MSE) (+inf when every byte equals its target)
+__global__ __launch_bounds__(1024) void metrics_reduce_kernel(int nparts, const float* __restrict__ part,
+                                                              double inv_n1, double inv_np,
+                                                              float* __restrict__ metrics) {
+    __shared__ double s_s[1024], s_m[1024], s_r[1024];
+    double a = 0.0, m = 0.0, r = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 1024) {
+        a += (double)part[kMetricParts * i];
+        m += (double)part[kMetricParts * i + 1];
+        r += (double)part[kMetricParts * i + 2];
+    }
+    s_s[threadIdx.x] = a;
+    s_m[threadIdx.x] = m;
+    s_r[threadIdx.x] = r;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            s_s[threadIdx.x] += s_s[threadIdx.x + o];
+            s_m[threadIdx.x] += s_m[threadIdx.x + o];
+            s_r[threadIdx.x] += s_r[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float mse = (float)(s_m[0] * inv_n1);
+        metrics[0] = -10.0f * log10f(mse);
+        metrics[1] = (float)(s_s[0] * inv_np);
+        metrics[2] = mse;
+        metrics[3] = (float)(s_r[0] * inv_n1);
+    }
+}
+
+template <int DT, int CH>
+void launch_metrics(const FwdLaunch& a, unsigned char* rgb_u8_out) {
+    metrics_fwd_kernel<DT, CH><<<a.grid, 256, 0, a.st>>>(a.H, a.W, a.C, a.img, a.tex, a.alpha, a.bg, (GtPtr<DT>)a.gt,
+                                                         a.win, a.rgb_out, rgb_u8_out, a.gt_out, a.part);
+}
+
+}  // namespace
+
+// workspace: the forward's per-workgroup partial records, nothing else
+extern "C" size_t gstex_eval_metrics_workspace_size(int32_t H, int32_t W) {
+    if (H <= kHalo || W <= kHalo) return 0;
+    dim3 g;
+    return (size_t)loss_grid(H, W, g) * kMetricParts * sizeof(float);
+}
+
+extern "C" int gstex_eval_metrics(int32_t H, int32_t W, int32_t C, const float* img, const float* tex,
+                                  const float* alpha, const float* background, const gstex_loss_target* target,
+                                  const float* window, float* rgb_out, uint8_t* rgb_u8_out, float* gt_out,
+                                  float* metrics_out, void* workspace, size_t workspace_bytes, void* stream) {
+    // the reference's evaluation applies no mask: a descriptor that carries one is a caller's mistake, not ignored
+    const char* bad = target && target->gt && target->mask ? "a mask is not supported (the evaluation applies none)"
+                                                           : target_error(target);
+    GSTEX_REQUIRE(!bad, "gstex_eval_metrics: %s", bad);
+    GSTEX_REQUIRE(H > kHalo && W > kHalo, "gstex_eval_metrics: image must be larger than the %d-tap window (%dx%d)",
+                  kWin, H, W);
+    GSTEX_REQUIRE(C >= 3 && C <= 8, "gstex_eval_metrics: tex channels must be in [3, 8] (got %d)", C);
+    GSTEX_REQUIRE(img && tex && alpha && background && window && metrics_out, "gstex_eval_metrics: null pointer");
+    GSTEX_REQUIRE(workspace && workspace_bytes >= gstex_eval_metrics_workspace_size(H, W),
+                  "gstex_eval_metrics: workspace too small");
+    FwdLaunch a;
+    a.st = as_stream(stream);
+    a.H = H, a.W = W, a.C = C;
+    a.img = img, a.tex = tex, a.alpha = alpha, a.bg = background;
+    a.gt = target->gt, a.mask = nullptr;
+    for (int k = 0; k < kWin; ++k) a.win.w[k] = window[k];  // host array
+    a.rgb_out = rgb_out, a.gt_out = gt_out;
+    a.gmaps = nullptr;
+    a.part = (float*)workspace;
+    const int nparts = loss_grid(H, W, a.grid);
+    if (target->gt_dtype == GSTEX_GT_U8) {
+        if (target->gt_channels == 4) launch_metrics<GSTEX_GT_U8, 4>(a, rgb_u8_out);
+        else launch_metrics<GSTEX_GT_U8, 3>(a, rgb_u8_out);
+    } else {
+        if (target->gt_channels == 4) launch_metrics<GSTEX_GT_F32, 4>(a, rgb_u8_out);
+        else launch_metrics<GSTEX_GT_F32, 3>(a, rgb_u8_out);
+    }
+    metrics_reduce_kernel<<<1, 1024, 0, a.st>>>(nparts, a.part, 1.0 / (3.0 * H * W),
+                                                1.0 / (3.0 * (H - kHalo) * (W - kHalo)), metrics_out);
+    return launch_status("gstex_eval_metrics");
+}

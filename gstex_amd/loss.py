@@ -9,6 +9,10 @@ the ~40 elementwise kernels and four GEMMs the same expression costs in eager Py
 ``image_loss(img, tex, alpha, background, image, mask=None)`` is the same loss on the image a dataset delivers
 (``gstex_loss_target_fwd`` / ``_bwd``): a uint8 or float32 target with 3 or 4 channels, an optional mask, and the
 step's MSE (for PSNR) from the same launch; ``image_loss_eager`` restates it with torch ops.
+
+``image_metrics(img, tex, alpha, background, image)`` is one view's evaluation by the reference's protocol
+(``gstex_eval_metrics``): PSNR and SSIM of the uint8-quantised render against the composited target, forward only;
+``image_metrics_eager`` restates it with torch ops.
 """
 from __future__ import annotations
 
@@ -135,23 +139,23 @@ def _check_target(name, alpha, image, mask):
     return mask
 
 
-def _check_image(img, tex, alpha, background, image, mask):
+def _check_image(img, tex, alpha, background, image, mask, fn="image_loss"):
     """Shapes and dtypes first, then the window, then the device: each refusal names what is wrong with the call."""
     if alpha.dim() != 2:
-        raise ValueError("image_loss: alpha must be a CUDA fp32 tensor of shape (H, W)")
+        raise ValueError(f"{fn}: alpha must be a CUDA fp32 tensor of shape (H, W)")
     H, W = alpha.shape
     for name, t, shape in (("img", img, (H, W, 3)), ("alpha", alpha, (H, W)), ("background", background, (3,))):
         if tuple(t.shape) != shape or t.dtype != torch.float32:
-            raise ValueError(f"image_loss: {name} must be a CUDA fp32 tensor of shape {shape}")
+            raise ValueError(f"{fn}: {name} must be a CUDA fp32 tensor of shape {shape}")
     if tex.dim() != 3 or tuple(tex.shape[:2]) != (H, W) or not 3 <= tex.shape[2] <= 8 or tex.dtype != torch.float32:
-        raise ValueError("image_loss: tex must be CUDA fp32 (H, W, C) with 3 <= C <= 8")
-    mask = _check_target("image_loss", alpha, image, mask)
+        raise ValueError(f"{fn}: tex must be CUDA fp32 (H, W, C) with 3 <= C <= 8")
+    mask = _check_target(fn, alpha, image, mask)
     if H <= 10 or W <= 10:
-        raise ValueError("image_loss: the image must be larger than the 11-tap SSIM window")
+        raise ValueError(f"{fn}: the image must be larger than the 11-tap SSIM window")
     for name, t in (("img", img), ("tex", tex), ("alpha", alpha), ("background", background), ("image", image),
                     ("mask", mask)):
         if t is not None and not t.is_cuda:
-            raise ValueError(f"image_loss: {name} must be a CUDA tensor")
+            raise ValueError(f"{fn}: {name} must be a CUDA tensor")
     return mask
 
 
@@ -249,6 +253,106 @@ def image_loss_eager(rgb, background, image, mask=None, ssim_lambda: float = 0.2
     loss = (1 - ssim_lambda) * l1 + ssim_lambda * (1 - sim)
     terms = torch.stack([loss.detach(), l1.detach(), sim.detach(), mse])
     return ImageLoss(loss, rgb.detach(), gt, terms)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# one view's evaluation metrics by the reference's protocol (gstex.py:1337-1403): PSNR / SSIM on the uint8 render
+# ---------------------------------------------------------------------------------------------------------------
+@dataclass
+class ImageMetrics:
+    """What image_metrics / image_metrics_eager return.  rgb: the composited render, outputs["rgb"] (H, W, 3) float32;
+    rgb_u8: its quantisation (255.0 * rgb).to(uint8) (H, W, 3), the bytes the reference writes to its PNGs; gt: the
+    composited target (H, W, 3) float32; metrics: four floats [PSNR, SSIM, MSE, MSE_raw] on the device -- PSNR, SSIM
+    and MSE of the quantised render (get_image_metrics_and_images), MSE_raw of the unquantised one (get_metrics_dict).
+    The properties are 0-dim views of `metrics`: nothing is read back to the host."""
+    rgb: torch.Tensor
+    rgb_u8: torch.Tensor
+    gt: torch.Tensor
+    metrics: torch.Tensor
+
+    @property
+    def psnr(self) -> torch.Tensor:
+        return self.metrics[0]
+
+    @property
+    def ssim(self) -> torch.Tensor:
+        return self.metrics[1]
+
+    @property
+    def mse(self) -> torch.Tensor:
+        return self.metrics[2]
+
+    @property
+    def mse_raw(self) -> torch.Tensor:
+        return self.metrics[3]
+
+
+def _check_out(fn, out):
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.numel() != 4
+                            or not out.is_contiguous()):
+        raise ValueError(f"{fn}: out must be a contiguous CUDA fp32 tensor of 4 elements")
+
+
+@torch.no_grad()
+def image_metrics(img, tex, alpha, background, image, out=None) -> ImageMetrics:
+    """PSNR, SSIM and MSE of one view as get_image_metrics_and_images takes them (gstex.py:1337-1403), on the raw
+    rasterizer outputs and the image a dataset delivers, in one launch pair (gstex_eval_metrics): the composite and
+    clamp, the uint8 quantisation of the render (255.0 * rgb).to(uint8).float() / 255.0, the target's conversion and
+    alpha composite on `background` (as image_loss; no mask: the reference's evaluation applies none), and the
+    reduction to [PSNR, SSIM, MSE, MSE_raw] on the device.  Not differentiable.  `out`: a contiguous CUDA float32
+    tensor of 4 elements the metrics are written into (one row of a per-image table)."""
+    fn = "image_metrics"
+    _check_out(fn, out)
+    _check_image(img, tex, alpha, background, image, None, fn=fn)
+    if out is not None and (not out.is_cuda or out.device != img.device):
+        raise ValueError(f"{fn}: out must be a contiguous CUDA fp32 tensor of 4 elements on the images' device")
+    img, tex, alpha, background = (t.detach().contiguous() for t in (img, tex, alpha, background))
+    image = _aligned(image.detach().contiguous(), 16)
+    H, W = alpha.shape
+    C = tex.shape[2]
+    dev = img.device
+    ws = torch.empty((int(_lib.load().gstex_eval_metrics_workspace_size(H, W)),), device=dev, dtype=torch.uint8)
+    metrics = out if out is not None else torch.empty((4,), device=dev, dtype=torch.float32)
+    rgb = torch.empty((H, W, 3), device=dev, dtype=torch.float32)
+    rgb_u8 = torch.empty((H, W, 3), device=dev, dtype=torch.uint8)
+    gt = torch.empty((H, W, 3), device=dev, dtype=torch.float32)
+    target = _loss_target(image, None)
+    call("gstex_eval_metrics", H, W, C, ptr(img), ptr(tex), ptr(alpha), ptr(background), ctypes.byref(target),
+         _cwin(), ptr(rgb), ptr(rgb_u8), ptr(gt), ptr(metrics), ptr(ws), ws.numel(), _lib.stream_of(dev))
+    return ImageMetrics(rgb, rgb_u8, gt, metrics)
+
+
+@torch.no_grad()
+def image_metrics_eager(rgb, background, image) -> ImageMetrics:
+    """image_metrics with torch ops on the composited render `rgb`: the reference's own expressions (get_gt_img and
+    composite_with_background, gstex.py:1244-1245, 1256-1258; the quantisation and the metrics, :1375-1384, with
+    PeakSignalNoiseRatio(data_range=1) = -10 log10(MSE) and this project's restatement of pytorch_msssim's SSIM).
+    Runs on any device; the trainer's fused_loss=False path and the tests' reference."""
+    from .model import ssim  # (model imports this module)
+
+    if rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise ValueError("image_metrics_eager: rgb must have shape (H, W, 3)")
+    _check_target("image_metrics_eager", rgb[..., 0], image, None)
+    rgb = rgb.detach()
+    if image.dtype == torch.uint8:
+        # get_gt_img divides on the CPU, a true division: a tensor divisor gives that on every device (see
+        # image_loss_eager)
+        image = image.float() / torch.full((), 255.0, device=image.device)
+    if image.shape[2] == 4:
+        a = image[..., -1].unsqueeze(-1).repeat((1, 1, 3))
+        gt = a * image[..., :3] + (1 - a) * background
+    else:
+        gt = image
+    gt_r = torch.moveaxis(gt, -1, 0)[None, ...]
+    pred = torch.moveaxis(rgb, -1, 0)[None, ...]
+    q = (255.0 * pred).to(dtype=torch.uint8)
+    pred = q.to(dtype=torch.float32) / 255.0
+    mse = torch.mean((pred - gt_r) ** 2)
+    psnr = -10.0 * torch.log10(mse)
+    sim = ssim(gt_r, pred)
+    mse_raw = torch.mean((rgb - gt) ** 2)
+    metrics = torch.stack([psnr, sim, mse, mse_raw]).to(torch.float32)
+    return ImageMetrics(rgb, torch.moveaxis(q[0], 0, -1).contiguous(), gt, metrics)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -29,8 +29,8 @@ import torch.nn.functional as F
 
 from . import ops
 from .activations import activate, sh_rest
-from .loss import (depth_to_normal, gaussian_window, geometry_loss, image_loss, image_loss_eager, photometric_loss,
-                   scheduled)
+from .loss import (ImageMetrics, depth_to_normal, gaussian_window, geometry_loss, image_loss, image_loss_eager,
+                   image_metrics, image_metrics_eager, photometric_loss, scheduled)
 from .optim import FusedAdam
 from .charts import SH2RGB, build_charts, get_uv_mapping, texture_dims_to_query
 from .scene import Scene, View
@@ -484,6 +484,53 @@ class GStexTrainer:
                     uv_im=torch.clamp(zeros3 + (1 - t_out[3][..., None]) * bg, 0.0, 1.0),
                     edit_img=torch.clamp(img + edit_tex_img + (1 - alpha[..., None]) * bg, 0.0, 1.0),
                     clean_normal_img=torch.clamp(0.5 * (n_unit + 1) + (1 - alpha[..., None]) * bg, 0.0, 1.0))
+
+    @torch.no_grad()
+    def evaluate(self, view: View, image: torch.Tensor, out: torch.Tensor | None = None) -> ImageMetrics:
+        """One view scored by the reference's protocol (get_image_metrics_and_images, gstex.py:1337-1403): one plain
+        render (the per-op path, no geometry outputs: none of eval_render's viewer images) at the current SH degree on
+        the evaluation background (the viewer colour under background="random", gstex.py:1021-1025), then PSNR and
+        SSIM of the uint8-quantised render against `image` as the dataset delivers it (gstex_amd.loss.image_metrics;
+        image_metrics_eager on the composited render with fused_loss=False).  out: a 4-element device fp32 tensor the
+        metrics are written into.  The training state is left alone: a pending deferred texel update is run (it
+        would run before the next render anyway), nothing else is touched."""
+        self.wait_texture()
+        r = self.render(view, composite=False, geometry=False)
+        bg = self._eval_background
+        if self.fused_loss:
+            return image_metrics(r["img"], r["tex"], r["alpha"], bg, image, out=out)
+        rgb = torch.clamp(r["img"] + r["tex"][:, :, 0:3] + (1 - r["alpha"][:, :, None]) * bg[None, None, :], 0.0, 1.0)
+        res = image_metrics_eager(rgb, bg, image)
+        if out is not None:
+            out.copy_(res.metrics)
+            res.metrics = out
+        return res
+
+    def evaluate_split(self, pairs, output_dir=None) -> dict:
+        """A test split scored as get_average_eval_image_metrics does (pipelines/base_pipeline.py:347-410): every
+        (View, image) of `pairs` (as gstex_amd.data.load_blender yields them) through evaluate(), image i's metrics
+        in row i of one (n, 4) device table that is read back once, after the loop.  Returns psnr, ssim, mse and
+        mse_raw, each the float64 mean of the per-image values (the mean of the PSNRs, not the PSNR of the mean MSE),
+        gaussian_count, texel_count and per_image (the table on the CPU, columns [PSNR, SSIM, MSE, MSE_raw]).
+        There is no lpips key: the LPIPS network's weights are not part of this project, and a made-up 0 would be
+        worse than an absent key.  output_dir: also write "{i:06d}-img.png", the reference's `img` (the target's
+        (gt * 255).byte() and the render's bytes side by side, base_pipeline.py:383-387)."""
+        pairs = list(pairs)
+        if not pairs:
+            raise ValueError("evaluate_split: no (view, image) pairs")
+        table = torch.zeros((len(pairs), 4), device=self.device, dtype=torch.float32)
+        for i, (view, image) in enumerate(pairs):
+            res = self.evaluate(view.to(self.device), image.to(self.device), out=table[i])
+            if output_dir is not None:
+                from PIL import Image  # (lazily, as gstex_amd.data)
+
+                both = torch.cat([(res.gt * 255).byte(), res.rgb_u8], dim=1)
+                Image.fromarray(both.cpu().numpy()).save(os.path.join(str(output_dir), f"{i:06d}-img.png"))
+        per_image = table.cpu()
+        mean = per_image.double().mean(dim=0)
+        return dict(psnr=float(mean[0]), ssim=float(mean[1]), mse=float(mean[2]), mse_raw=float(mean[3]),
+                    gaussian_count=float(self.means.shape[0]), texel_count=float(self.n_texels),
+                    per_image=per_image)
 
     def loss(self, rgb: torch.Tensor, gt: torch.Tensor, ssim_lambda: float = 0.2) -> torch.Tensor:
         l1 = torch.abs(gt - rgb).mean()

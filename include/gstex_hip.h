@@ -47,7 +47,8 @@ extern "C" {
  * ABI 18 (round 6): the hipGraph step support of ABI 16 (event-record nodes, gstex_adam_step_scheduled) and the
  * split-backward settings bit of ABI 15 are removed (measured slower).
  * The number counts incompatible changes: an addition that leaves every existing symbol's signature and meaning alone
- * keeps it, and is marked "added within ABI 19 (additive)" where it is declared (gstex_loss_target_*). */
+ * keeps it, and is marked "added within ABI 19 (additive)" where it is declared (gstex_loss_target_*,
+ * gstex_eval_metrics*). */
 #define GSTEX_ABI_VERSION 19
 
 /* Per-record layout of the splat table written by gstex_raster_setup (floats). */
@@ -428,6 +429,30 @@ int gstex_loss_target_bwd(int32_t H, int32_t W, int32_t C, const float* img, con
                           const float* background, const gstex_loss_target* target, const float* window,
                           float ssim_lambda, const float* grad_loss, float* d_img, float* d_tex, float* d_alpha,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* One view's evaluation metrics by the reference's protocol -- added within ABI 19 (additive).
+ * get_image_metrics_and_images (gstex.py:1337-1403): the render is quantised to uint8 (:1379-1381) before PSNR and
+ * SSIM are taken against the composited target; forward only (no gradient maps, no backward).
+ * Each line is one individually rounded fp32 operation:
+ *   rgb_c = as gstex_loss_fwd (outputs["rgb"], clamped)
+ *   q_c   = (uint8)(255.0f * rgb_c)                  (truncation, as (255.0 * x).to(torch.uint8))
+ *   y_c   = (float)q_c * (1.0f / 255.0f)             (as torch's device kernel evaluates .to(float32) / 255.0)
+ *   gt_c  = as gstex_loss_target_fwd: the stored value (F32) or (float)v / 255.0f (U8); with four channels
+ *           a * g_c + (1 - a) * background_c.  No mask: the reference's evaluation applies none.
+ *   MSE     = mean (y_c - gt_c)^2
+ *   SSIM    = SSIM(X = gt, Y = y) as gstex_loss_fwd (window, constants, valid filtering, fixed-order reduction)
+ *   MSE_raw = mean (rgb_c - gt_c)^2                  (the unquantised value of get_metrics_dict)
+ *   metrics_out (device float[4]) = {PSNR = -10 log10(MSE) (+inf for MSE = 0), SSIM, MSE, MSE_raw}
+ * Optional outputs, each nullable: rgb_out (H*W*3 floats, rgb, unquantised), rgb_u8_out (H*W*3 bytes, q: the bytes
+ * the reference writes to its PNGs, (val * 255).byte()), gt_out (H*W*3 floats, gt).
+ * The target is the gstex_loss_target of gstex_loss_target_fwd with the same alignment rules; a non-NULL mask is
+ * rejected, `reserved` must be 0.  The workspace is gstex_eval_metrics_workspace_size bytes (0 when H or W <= 10):
+ * three floats per forward workgroup (ceil(W / 16) * ceil(H / 16) * 3 of them), nothing else. */
+size_t gstex_eval_metrics_workspace_size(int32_t H, int32_t W);
+int gstex_eval_metrics(int32_t H, int32_t W, int32_t C, const float* img, const float* tex, const float* alpha,
+                       const float* background, const gstex_loss_target* target, const float* window,
+                       float* rgb_out, uint8_t* rgb_u8_out, float* gt_out, float* metrics_out, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* ---- optimizer (train-step support) ----------------------------------- */
 /* One launch of torch.optim.Adam (no weight decay, no amsgrad) over up to GSTEX_ADAM_MAX_TENSORS
