@@ -25,8 +25,13 @@
 //
 //   gstex_eval_metrics               <- the evaluation protocol of get_image_metrics_and_images (gstex.py:1337-1403) on
 //                                       one view: the render quantised to uint8 (:1379-1381) in the staging loop, PSNR
-//                                       and SSIM against the composited target.  A forward-only sibling of the loss
-//                                       forward (metrics_fwd_kernel, at the end of this file): no gmaps, no mask, no L1.
+//                                       and SSIM against the composited target.  Forward only (metrics_fwd_kernel): no
+//                                       gmaps, no mask, no L1.
+//
+// Stated once, for both forwards: the row and column filters, the SSIM point and the workgroup's partial sums
+// (ssim_rows, ssim_columns, ssim_point, block_sums); the fp64 reduction of the partial records (reduce_kernel); and on
+// the host the argument checks, the launch description and the dtype x channels x mask dispatch of all five entry
+// points.  The two forward kernels differ in their staging loops only.
 #include "gstex_common.h"
 #include "gstex_error.h"
 
@@ -137,15 +142,95 @@ __device__ __forceinline__ LossTile loss_tile() {
     return LossTile{t % gx, (t / gx) % gy, t / (gx * gy)};
 }
 
-// the forward's partial record: {sum s, sum |X - Y|} or, for the dataset targets, three floats (+ sum (rgb - gt)^2)
-template <bool EXT>
-struct PartRecord {
-    using type = float2;
+// ---- the SSIM tile pipeline of both forward kernels -------------------------------------------------------------
+// Each piece carries its own contraction pragma (fused multiply-adds: the window sums need no fixed operation order --
+// the loss and its gradient are compared with tolerances, only the composite bit for bit).  The staging loops that fill
+// s_x / s_y stay in the kernels, outside it.
+
+// rows: 26 x 16 horizontal filters of the five window moments of the staged X and Y
+__device__ __forceinline__ void ssim_rows(const Win& win, const float (&s_x)[kReg][kReg + 1],
+                                          const float (&s_y)[kReg][kReg + 1], float (&s_h)[5][kReg][kLT + 1]) {
+    for (int i = threadIdx.x; i < kReg * kLT; i += 256) {
+#pragma clang fp contract(fast)
+        const int ry = i / kLT, cx = i % kLT;
+        float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
+#pragma unroll
+        for (int k = 0; k < kWin; ++k) {
+            const float xv = s_x[ry][cx + k], yv = s_y[ry][cx + k];
+            a += win.w[k] * xv;
+            b += win.w[k] * yv;
+            aa += win.w[k] * (xv * xv);
+            bb += win.w[k] * (yv * yv);
+            ab += win.w[k] * (xv * yv);
+        }
+        s_h[0][ry][cx] = a;
+        s_h[1][ry][cx] = b;
+        s_h[2][ry][cx] = aa;
+        s_h[3][ry][cx] = bb;
+        s_h[4][ry][cx] = ab;
+    }
+}
+
+// columns: q = {mu1, mu2, E[X^2], E[Y^2], E[XY]} at tile position (cy, cx)
+__device__ __forceinline__ void ssim_columns(const Win& win, const float (&s_h)[5][kReg][kLT + 1], int cy, int cx,
+                                             float (&q)[5]) {
+#pragma clang fp contract(fast)
+#pragma unroll
+    for (int m = 0; m < 5; ++m) q[m] = 0.f;
+#pragma unroll
+    for (int k = 0; k < kWin; ++k)
+#pragma unroll
+        for (int m = 0; m < 5; ++m) q[m] += win.w[k] * s_h[m][cy + k][cx];
+}
+
+// the SSIM map's value s at one position, with the terms its derivatives are made of
+struct SsimPoint {
+    float mu1, mu2, A, B, Cc, D, s;
 };
-template <>
-struct PartRecord<true> {
-    using type = float;
-};
+__device__ __forceinline__ SsimPoint ssim_point(const float (&q)[5]) {
+#pragma clang fp contract(fast)
+    const float mu1 = q[0], mu2 = q[1];
+    const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
+    const float s11 = q[2] - mu1_sq, s22 = q[3] - mu2_sq, s12 = q[4] - mu1_mu2;
+    const float A = 2.0f * mu1_mu2 + kC1, B = 2.0f * s12 + kC2;
+    const float Cc = mu1_sq + mu2_sq + kC1, D = s11 + s22 + kC2;
+    const float cs = B / D;
+    return SsimPoint{mu1, mu2, A, B, Cc, D, (A / Cc) * cs};
+}
+
+// what the backward filters (the loss forward only): g = {dS/d mu2 in full, dS/dE[Y^2], dS/dE[XY]}
+__device__ __forceinline__ void ssim_point_gmaps(const SsimPoint& p, float (&g)[3]) {
+#pragma clang fp contract(fast)
+    // dS/d mu2 (through mu2, sigma2^2 = E[Y^2] - mu2^2, sigma12 = E[XY] - mu1 mu2), dS/dE[Y^2], dS/dE[XY]
+    const float ds_dmu2 = p.s * (2.0f * p.mu1 / p.A - 2.0f * p.mu2 / p.Cc);
+    const float ds_ds22 = -p.s / p.D;
+    const float ds_ds12 = 2.0f * p.s / p.B;
+    g[0] = ds_dmu2 - 2.0f * p.mu2 * ds_ds22 - p.mu1 * ds_ds12;
+    g[1] = ds_ds22;
+    g[2] = ds_ds12;
+}
+
+// The workgroup's sums of N per-thread values, stored as partial record b = part[N * b ..] with b the tile index (not
+// the launch slot): wave reduce, then the 4 waves in order, so the reduction order is fixed.  Every thread calls it.
+template <int N>
+__device__ __forceinline__ void block_sums(float (&v)[N], const LossTile& lt, float* __restrict__ part) {
+    __shared__ float s_red[N][4];
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int m = 0; m < N; ++m) v[m] += __shfl_xor(v[m], off, 64);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int m = 0; m < N; ++m) s_red[m][tid >> 6] = v[m];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int b = (lt.c * gridDim.y + lt.by) * gridDim.x + lt.bx;
+#pragma unroll
+        for (int m = 0; m < N; ++m) part[N * b + m] = ((s_red[m][0] + s_red[m][1]) + s_red[m][2]) + s_red[m][3];
+    }
+}
 
 // What only the dataset-target instantiations take, as a trailing kernel argument: empty for gstex_loss_fwd / _bwd,
 // whose kernels keep the argument layout (and so the code) they had before the policy.
@@ -172,12 +257,10 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(int H, int W, int C, cons
                                                        const float* __restrict__ bg,
                                                        GtPtr<DT> __restrict__ gt, Win win,
                                                        float* __restrict__ rgb_out,
-                                                       float* __restrict__ gmaps,
-                                                       typename PartRecord<EXT>::type* __restrict__ part,
+                                                       float* __restrict__ gmaps, float* __restrict__ part,
                                                        FwdExtra<EXT> ex) {
     __shared__ float s_x[kReg][kReg + 1], s_y[kReg][kReg + 1];
     __shared__ float s_h[5][kReg][kLT + 1];
-    __shared__ float s_red[EXT ? 3 : 2][8];
     const LossTile lt = loss_tile();
     const int c = lt.c;
     const int x0 = lt.bx * kLT, y0 = lt.by * kLT;
@@ -218,144 +301,90 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(int H, int W, int C, cons
         s_y[ry][rx] = yv;
     }
     __syncthreads();
-    // rows: 26 x 16 horizontal filters of the five quantities (fused multiply-adds: the window sums need no fixed
-    // operation order -- the loss and its gradient are compared with tolerances, only the composite bit for bit)
-    for (int i = tid; i < kReg * kLT; i += 256) {
-#pragma clang fp contract(fast)
-        const int ry = i / kLT, cx = i % kLT;
-        float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
-#pragma unroll
-        for (int k = 0; k < kWin; ++k) {
-            const float xv = s_x[ry][cx + k], yv = s_y[ry][cx + k];
-            a += win.w[k] * xv;
-            b += win.w[k] * yv;
-            aa += win.w[k] * (xv * xv);
-            bb += win.w[k] * (yv * yv);
-            ab += win.w[k] * (xv * yv);
-        }
-        s_h[0][ry][cx] = a;
-        s_h[1][ry][cx] = b;
-        s_h[2][ry][cx] = aa;
-        s_h[3][ry][cx] = bb;
-        s_h[4][ry][cx] = ab;
-    }
+    // a local copy: the compiler then issues the window's kernel-argument loads with the others at entry, ahead of the
+    // first wait, and keeps 8 SGPRs fewer (measured: 0.3-0.4 us of the 800x800 forward + backward pair, EXPERIMENTS.md
+    // "loss.hip refactor"; metrics_fwd_kernel loads everything at entry without one)
+    const Win w = win;
+    ssim_rows(w, s_x, s_y, s_h);
     __syncthreads();
     // columns + the SSIM map at this thread's position
     const int cy = tid >> 4, cx = tid & 15;
     const int py = y0 + cy, px = x0 + cx;
-    float ssum = 0.f;
+    constexpr int N = EXT ? 3 : 2;  // the partial record: {sum s, sum |X - Y|} (+ sum (rgb - gt)^2)
+    float sums[N] = {};
     if (py < Hv && px < Wv) {
-#pragma clang fp contract(fast)
-        float q[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < kWin; ++k)
-#pragma unroll
-            for (int m = 0; m < 5; ++m) q[m] += win.w[k] * s_h[m][cy + k][cx];
-        const float mu1 = q[0], mu2 = q[1];
-        const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
-        const float s11 = q[2] - mu1_sq, s22 = q[3] - mu2_sq, s12 = q[4] - mu1_mu2;
-        const float A = 2.0f * mu1_mu2 + kC1, B = 2.0f * s12 + kC2;
-        const float Cc = mu1_sq + mu2_sq + kC1, D = s11 + s22 + kC2;
-        const float cs = B / D;
-        const float s = (A / Cc) * cs;
-        ssum = s;
-        // dS/d mu2 (through mu2, sigma2^2 = E[Y^2] - mu2^2, sigma12 = E[XY] - mu1 mu2), dS/dE[Y^2], dS/dE[XY]
-        const float ds_dmu2 = s * (2.0f * mu1 / A - 2.0f * mu2 / Cc);
-        const float ds_ds22 = -s / D;
-        const float ds_ds12 = 2.0f * s / B;
+        float q[5], g[3];
+        ssim_columns(w, s_h, cy, cx, q);
+        const SsimPoint p = ssim_point(q);
+        ssim_point_gmaps(p, g);
+        sums[0] = p.s;
         const size_t o = ((size_t)c * Hv + py) * Wv + px;
         const size_t plane = (size_t)3 * Hv * Wv;
-        gmaps[o] = ds_dmu2 - 2.0f * mu2 * ds_ds22 - mu1 * ds_ds12;
-        gmaps[plane + o] = ds_ds22;
-        gmaps[2 * plane + o] = ds_ds12;
+        gmaps[o] = g[0];
+        gmaps[plane + o] = g[1];
+        gmaps[2 * plane + o] = g[2];
     }
-    // workgroup sums (fixed order: wave reduce, then the 4 waves in order)
+    sums[1] = l1;
+    if constexpr (EXT) sums[2] = mse;
+    block_sums<N>(sums, lt, part);
+}
+
+// The partial records' sums: one workgroup, fp64, a strided accumulation and a 512 -> 1 tree (one fixed order), then
+// `finish` turns the N sums into the output floats.
+template <int N, class Finish>
+__global__ __launch_bounds__(1024) void reduce_kernel(int nparts, const float* __restrict__ part, Finish finish,
+                                                      float* __restrict__ out) {
+    __shared__ double s_sum[N][1024];
+    double acc[N] = {};
+    for (int i = threadIdx.x; i < nparts; i += 1024) {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        ssum += __shfl_xor(ssum, off, 64);
-        l1 += __shfl_xor(l1, off, 64);
-        if constexpr (EXT) mse += __shfl_xor(mse, off, 64);
+        for (int m = 0; m < N; ++m) acc[m] += (double)part[N * i + m];
     }
-    if ((tid & 63) == 0) {
-        s_red[0][tid >> 6] = ssum;
-        s_red[1][tid >> 6] = l1;
-        if constexpr (EXT) s_red[2][tid >> 6] = mse;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const int b = (lt.c * gridDim.y + lt.by) * gridDim.x + lt.bx;  // tile index: fixed reduction order
-        const float ps = ((s_red[0][0] + s_red[0][1]) + s_red[0][2]) + s_red[0][3];
-        const float pl = ((s_red[1][0] + s_red[1][1]) + s_red[1][2]) + s_red[1][3];
-        if constexpr (EXT) {
-            part[3 * b] = ps;
-            part[3 * b + 1] = pl;
-            part[3 * b + 2] = ((s_red[2][0] + s_red[2][1]) + s_red[2][2]) + s_red[2][3];
-        } else {
-            part[b] = make_float2(ps, pl);
-        }
-    }
-}
-
-__global__ __launch_bounds__(1024) void loss_reduce_kernel(int nparts, const float2* __restrict__ part, double inv_n1,
-                                                           double inv_np, float w_l1, float w_ssim,
-                                                           float* __restrict__ loss) {
-    __shared__ double s_s[1024], s_l[1024];
-    double a = 0.0, b = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 1024) {
-        a += (double)part[i].x;
-        b += (double)part[i].y;
-    }
-    s_s[threadIdx.x] = a;
-    s_l[threadIdx.x] = b;
+#pragma unroll
+    for (int m = 0; m < N; ++m) s_sum[m][threadIdx.x] = acc[m];
     __syncthreads();
     for (int o = 512; o > 0; o >>= 1) {
         if ((int)threadIdx.x < o) {
-            s_s[threadIdx.x] += s_s[threadIdx.x + o];
-            s_l[threadIdx.x] += s_l[threadIdx.x + o];
+#pragma unroll
+            for (int m = 0; m < N; ++m) s_sum[m][threadIdx.x] += s_sum[m][threadIdx.x + o];
         }
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        const float l1 = (float)(s_l[0] * inv_n1);
-        const float ssim = (float)(s_s[0] * inv_np);
-        loss[0] = w_l1 * l1 + w_ssim * (1.0f - ssim);
-        loss[1] = l1;
-        loss[2] = ssim;
+        double sums[N];
+#pragma unroll
+        for (int m = 0; m < N; ++m) sums[m] = s_sum[m][0];
+        finish(sums, out);
     }
 }
 
-// the target path's reduction: three partials per workgroup, terms = {loss, L1, SSIM, MSE}
-__global__ __launch_bounds__(1024) void loss_target_reduce_kernel(int nparts, const float* __restrict__ part,
-                                                                  double inv_n1, double inv_np, float w_l1,
-                                                                  float w_ssim, float* __restrict__ terms) {
-    __shared__ double s_s[1024], s_l[1024], s_m[1024];
-    double a = 0.0, b = 0.0, m = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 1024) {
-        a += (double)part[3 * i];
-        b += (double)part[3 * i + 1];
-        m += (double)part[3 * i + 2];
+// {loss, L1, SSIM} from {sum s, sum |X - Y|}; with the target path's third partial also the MSE
+struct LossFinish {
+    double inv_n1, inv_np;
+    float w_l1, w_ssim;
+    template <int N>
+    __device__ void operator()(const double (&sums)[N], float* out) const {
+        const float l1 = (float)(sums[1] * inv_n1);
+        const float ssim = (float)(sums[0] * inv_np);
+        out[0] = w_l1 * l1 + w_ssim * (1.0f - ssim);
+        out[1] = l1;
+        out[2] = ssim;
+        if constexpr (N == 3) out[3] = (float)(sums[2] * inv_n1);
     }
-    s_s[threadIdx.x] = a;
-    s_l[threadIdx.x] = b;
-    s_m[threadIdx.x] = m;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            s_s[threadIdx.x] += s_s[threadIdx.x + o];
-            s_l[threadIdx.x] += s_l[threadIdx.x + o];
-            s_m[threadIdx.x] += s_m[threadIdx.x + o];
-        }
-        __syncthreads();
+};
+
+// {PSNR, SSIM, MSE, MSE_raw} from {sum s, sum (y - gt)^2, sum (rgb - gt)^2}; PSNR = -10 log10(MSE) (+inf when every
+// byte equals its target)
+struct MetricsFinish {
+    double inv_n1, inv_np;
+    __device__ void operator()(const double (&sums)[3], float* out) const {
+        const float mse = (float)(sums[1] * inv_n1);
+        out[0] = -10.0f * log10f(mse);
+        out[1] = (float)(sums[0] * inv_np);
+        out[2] = mse;
+        out[3] = (float)(sums[2] * inv_n1);
     }
-    if (threadIdx.x == 0) {
-        const float l1 = (float)(s_l[0] * inv_n1);
-        const float ssim = (float)(s_s[0] * inv_np);
-        terms[0] = w_l1 * l1 + w_ssim * (1.0f - ssim);
-        terms[1] = l1;
-        terms[2] = ssim;
-        terms[3] = (float)(s_m[0] * inv_n1);
-    }
-}
+};
 
 template <int DT, int CH, int MK>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(int H, int W, int C, const float* __restrict__ img,
@@ -463,232 +492,7 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(int H, int W, int C, cons
     d_alpha[pix] = -((gch[0] * bg[0] + gch[1] * bg[1]) + gch[2] * bg[2]);
 }
 
-}  // namespace
-
-using namespace gstex;
-
-// forward: one workgroup per (tile, channel); backward: one per tile (its three channels in turn)
-static int loss_grid(int H, int W, dim3& grid, int channels = 3) {
-    grid = dim3((unsigned)((W + kLT - 1) / kLT), (unsigned)((H + kLT - 1) / kLT), (unsigned)channels);
-    return (int)(grid.x * grid.y * grid.z);
-}
-
-// workspace: the forward's per-workgroup partial records (part_floats each), then the gmaps
-static size_t loss_ws_size(int H, int W, int part_floats) {
-    if (H <= kHalo || W <= kHalo) return 0;
-    dim3 g;
-    const size_t parts = (size_t)loss_grid(H, W, g) * part_floats * sizeof(float);
-    const size_t gm = (size_t)3 * 3 * (H - kHalo) * (W - kHalo) * sizeof(float);
-    return ((parts + 255) & ~(size_t)255) + gm;
-}
-
-static void loss_ws(int H, int W, int part_floats, void* ws, float** part, float** gmaps) {
-    dim3 g;
-    const size_t parts = (size_t)loss_grid(H, W, g) * part_floats * sizeof(float);
-    char* b = (char*)ws;
-    *part = (float*)b;
-    b += (parts + 255) & ~(size_t)255;
-    *gmaps = (float*)b;
-}
-
-extern "C" size_t gstex_loss_workspace_size(int32_t H, int32_t W) { return loss_ws_size(H, W, 2); }
-
-extern "C" size_t gstex_loss_target_workspace_size(int32_t H, int32_t W) { return loss_ws_size(H, W, 3); }
-
-extern "C" int gstex_loss_fwd(int32_t H, int32_t W, int32_t C, const float* img, const float* tex,
-                              const float* alpha, const float* background, const float* gt, const float* window,
-                              float ssim_lambda, float* rgb_out, float* loss_out, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-    GSTEX_REQUIRE(H > kHalo && W > kHalo, "gstex_loss_fwd: image must be larger than the %d-tap window (%dx%d)",
-                  kWin, H, W);
-    GSTEX_REQUIRE(C >= 3 && C <= 8, "gstex_loss_fwd: tex channels must be in [3, 8] (got %d)", C);
-    GSTEX_REQUIRE(img && tex && alpha && background && gt && window && loss_out, "gstex_loss_fwd: null pointer");
-    GSTEX_REQUIRE(workspace && workspace_bytes >= gstex_loss_workspace_size(H, W),
-                  "gstex_loss_fwd: workspace too small");
-    Win win;
-    for (int k = 0; k < kWin; ++k) win.w[k] = window[k];  // host array
-    float *part, *gmaps;
-    loss_ws(H, W, 2, workspace, &part, &gmaps);
-    dim3 grid;
-    const int nparts = loss_grid(H, W, grid);
-    hipStream_t st = as_stream(stream);
-    loss_fwd_kernel<GSTEX_GT_F32, 3, kMaskNone, false><<<grid, 256, 0, st>>>(
-        H, W, C, img, tex, alpha, background, gt, win, rgb_out, gmaps, (float2*)part, FwdExtra<false>{});
-    loss_reduce_kernel<<<1, 1024, 0, st>>>(nparts, (const float2*)part, 1.0 / (3.0 * H * W),
-                                           1.0 / (3.0 * (H - kHalo) * (W - kHalo)), 1.0f - ssim_lambda, ssim_lambda,
-                                           loss_out);
-    return launch_status("gstex_loss_fwd");
-}
-
-extern "C" int gstex_loss_bwd(int32_t H, int32_t W, int32_t C, const float* img, const float* tex,
-                              const float* alpha, const float* background, const float* gt, const float* window,
-                              float ssim_lambda, const float* grad_loss, float* d_img, float* d_tex, float* d_alpha,
-                              void* workspace, size_t workspace_bytes, void* stream) {
-    GSTEX_REQUIRE(H > kHalo && W > kHalo, "gstex_loss_bwd: image must be larger than the %d-tap window", kWin);
-    GSTEX_REQUIRE(C >= 3 && C <= 8, "gstex_loss_bwd: tex channels must be in [3, 8] (got %d)", C);
-    GSTEX_REQUIRE(img && tex && alpha && background && gt && window && grad_loss && d_img && d_tex && d_alpha,
-                  "gstex_loss_bwd: null pointer");
-    GSTEX_REQUIRE(workspace && workspace_bytes >= gstex_loss_workspace_size(H, W),
-                  "gstex_loss_bwd: workspace too small");
-    Win win;
-    for (int k = 0; k < kWin; ++k) win.w[k] = window[k];
-    float *part, *gmaps;
-    loss_ws(H, W, 2, workspace, &part, &gmaps);
-    dim3 grid;
-    loss_grid(H, W, grid, 1);
-    hipStream_t st = as_stream(stream);
-    const float k_l1 = (float)((1.0 - ssim_lambda) / (3.0 * H * W));
-    const float k_ssim = (float)(ssim_lambda / (3.0 * (H - kHalo) * (W - kHalo)));
-    loss_bwd_kernel<GSTEX_GT_F32, 3, kMaskNone><<<grid, 256, 0, st>>>(
-        H, W, C, img, tex, alpha, background, gt, win, gmaps, grad_loss, k_l1, k_ssim, d_img, d_tex, d_alpha,
-        BwdExtra<kMaskNone>{});
-    return launch_status("gstex_loss_bwd");
-}
-
-// ---- dataset targets (uint8 / RGBA / mask) ---------------------------------------------------------------------
-namespace {
-
-struct FwdLaunch {
-    dim3 grid;
-    hipStream_t st;
-    int H, W, C;
-    const float *img, *tex, *alpha, *bg;
-    const void *gt, *mask;
-    Win win;
-    float *rgb_out, *gt_out, *gmaps, *part;
-};
-
-struct BwdLaunch {
-    dim3 grid;
-    hipStream_t st;
-    int H, W, C;
-    const float *img, *tex, *alpha, *bg;
-    const void *gt, *mask;
-    Win win;
-    const float *gmaps, *grad_loss;
-    float k_l1, k_ssim;
-    float *d_img, *d_tex, *d_alpha;
-};
-
-template <int DT, int CH, int MK>
-void launch(const FwdLaunch& a) {
-    loss_fwd_kernel<DT, CH, MK, true><<<a.grid, 256, 0, a.st>>>(a.H, a.W, a.C, a.img, a.tex, a.alpha, a.bg,
-                                                                (GtPtr<DT>)a.gt, a.win,
-                                                                a.rgb_out, a.gmaps, a.part,
-                                                                FwdExtra<true>{a.mask, a.gt_out});
-}
-
-template <int DT, int CH, int MK>
-void launch(const BwdLaunch& a) {
-    BwdExtra<MK> ex;
-    if constexpr (MK != kMaskNone) ex.mask = a.mask;
-    loss_bwd_kernel<DT, CH, MK><<<a.grid, 256, 0, a.st>>>(a.H, a.W, a.C, a.img, a.tex, a.alpha, a.bg,
-                                                          (GtPtr<DT>)a.gt, a.win,
-                                                          a.gmaps, a.grad_loss, a.k_l1, a.k_ssim, a.d_img, a.d_tex,
-                                                          a.d_alpha, ex);
-}
-
-template <int DT, int CH, class Args>
-void dispatch_mask(int mk, const Args& a) {
-    if (mk == kMaskNone) launch<DT, CH, kMaskNone>(a);
-    else if (mk == kMaskF32) launch<DT, CH, kMaskF32>(a);
-    else launch<DT, CH, kMaskBool>(a);
-}
-
-// the policy instantiation of a (validated) target descriptor
-template <class Args>
-void dispatch_target(const gstex_loss_target& t, const Args& a) {
-    const int mk = !t.mask ? kMaskNone : (t.mask_dtype == GSTEX_MASK_BOOL ? kMaskBool : kMaskF32);
-    if (t.gt_dtype == GSTEX_GT_U8) {
-        if (t.gt_channels == 4) dispatch_mask<GSTEX_GT_U8, 4>(mk, a);
-        else dispatch_mask<GSTEX_GT_U8, 3>(mk, a);
-    } else {
-        if (t.gt_channels == 4) dispatch_mask<GSTEX_GT_F32, 4>(mk, a);
-        else dispatch_mask<GSTEX_GT_F32, 3>(mk, a);
-    }
-}
-
-// 0, or the message of the first invalid field (nothing is launched for an invalid descriptor)
-const char* target_error(const gstex_loss_target* t) {
-    if (!t) return "null target";
-    if (!t->gt) return "null target gt";
-    if (t->gt_dtype != GSTEX_GT_F32 && t->gt_dtype != GSTEX_GT_U8) return "gt_dtype out of range";
-    if (t->gt_channels != 3 && t->gt_channels != 4) return "gt_channels must be 3 or 4";
-    if (t->mask && t->mask_dtype != GSTEX_MASK_F32 && t->mask_dtype != GSTEX_MASK_BOOL)
-        return "mask_dtype out of range";
-    if (t->reserved != 0) return "reserved must be 0";
-    // an RGBA pixel is read as one word / one float4; fp32 values and masks as floats
-    const size_t align = t->gt_dtype == GSTEX_GT_F32 ? (t->gt_channels == 4 ? 16 : 4) : (t->gt_channels == 4 ? 4 : 1);
-    if ((uintptr_t)t->gt % align != 0) return "target gt is not aligned to its pixel load";
-    if (t->mask && t->mask_dtype == GSTEX_MASK_F32 && (uintptr_t)t->mask % 4 != 0) return "mask is not aligned";
-    return nullptr;
-}
-
-}  // namespace
-
-extern "C" int gstex_loss_target_fwd(int32_t H, int32_t W, int32_t C, const float* img, const float* tex,
-                                     const float* alpha, const float* background, const gstex_loss_target* target,
-                                     const float* window, float ssim_lambda, float* rgb_out, float* gt_out,
-                                     float* terms_out, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* bad = target_error(target);
-    GSTEX_REQUIRE(!bad, "gstex_loss_target_fwd: %s", bad);
-    GSTEX_REQUIRE(H > kHalo && W > kHalo,
-                  "gstex_loss_target_fwd: image must be larger than the %d-tap window (%dx%d)", kWin, H, W);
-    GSTEX_REQUIRE(C >= 3 && C <= 8, "gstex_loss_target_fwd: tex channels must be in [3, 8] (got %d)", C);
-    GSTEX_REQUIRE(img && tex && alpha && background && window && terms_out, "gstex_loss_target_fwd: null pointer");
-    GSTEX_REQUIRE(workspace && workspace_bytes >= gstex_loss_target_workspace_size(H, W),
-                  "gstex_loss_target_fwd: workspace too small");
-    FwdLaunch a;
-    a.st = as_stream(stream);
-    a.H = H, a.W = W, a.C = C;
-    a.img = img, a.tex = tex, a.alpha = alpha, a.bg = background;
-    a.gt = target->gt, a.mask = target->mask;
-    for (int k = 0; k < kWin; ++k) a.win.w[k] = window[k];  // host array
-    a.rgb_out = rgb_out, a.gt_out = gt_out;
-    loss_ws(H, W, 3, workspace, &a.part, &a.gmaps);
-    const int nparts = loss_grid(H, W, a.grid);
-    dispatch_target(*target, a);
-    loss_target_reduce_kernel<<<1, 1024, 0, a.st>>>(nparts, a.part, 1.0 / (3.0 * H * W),
-                                                    1.0 / (3.0 * (H - kHalo) * (W - kHalo)), 1.0f - ssim_lambda,
-                                                    ssim_lambda, terms_out);
-    return launch_status("gstex_loss_target_fwd");
-}
-
-extern "C" int gstex_loss_target_bwd(int32_t H, int32_t W, int32_t C, const float* img, const float* tex,
-                                     const float* alpha, const float* background, const gstex_loss_target* target,
-                                     const float* window, float ssim_lambda, const float* grad_loss, float* d_img,
-                                     float* d_tex, float* d_alpha, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-    const char* bad = target_error(target);
-    GSTEX_REQUIRE(!bad, "gstex_loss_target_bwd: %s", bad);
-    GSTEX_REQUIRE(H > kHalo && W > kHalo, "gstex_loss_target_bwd: image must be larger than the %d-tap window", kWin);
-    GSTEX_REQUIRE(C >= 3 && C <= 8, "gstex_loss_target_bwd: tex channels must be in [3, 8] (got %d)", C);
-    GSTEX_REQUIRE(img && tex && alpha && background && window && grad_loss && d_img && d_tex && d_alpha,
-                  "gstex_loss_target_bwd: null pointer");
-    GSTEX_REQUIRE(workspace && workspace_bytes >= gstex_loss_target_workspace_size(H, W),
-                  "gstex_loss_target_bwd: workspace too small");
-    BwdLaunch a;
-    a.st = as_stream(stream);
-    a.H = H, a.W = W, a.C = C;
-    a.img = img, a.tex = tex, a.alpha = alpha, a.bg = background;
-    a.gt = target->gt, a.mask = target->mask;
-    for (int k = 0; k < kWin; ++k) a.win.w[k] = window[k];
-    float* part;
-    float* gmaps;
-    loss_ws(H, W, 3, workspace, &part, &gmaps);
-    a.gmaps = gmaps;
-    a.grad_loss = grad_loss;
-    a.k_l1 = (float)((1.0 - ssim_lambda) / (3.0 * H * W));
-    a.k_ssim = (float)(ssim_lambda / (3.0 * (H - kHalo) * (W - kHalo)));
-    a.d_img = d_img, a.d_tex = d_tex, a.d_alpha = d_alpha;
-    loss_grid(H, W, a.grid, 1);
-    dispatch_target(*target, a);
-    return launch_status("gstex_loss_target_bwd");
-}
-
 // ---- evaluation metrics (uint8-quantised PSNR / SSIM, forward only) ----------------------------------------------
-namespace {
-
 constexpr int kMetricParts = 3;  // per workgroup: {sum s, sum (y - gt)^2, sum (rgb - gt)^2}
 
 // The loss forward's tiling (one workgroup per 16x16 tile and channel, XCD-aware order) with the reference's uint8
@@ -705,7 +509,6 @@ __global__ __launch_bounds__(256) void metrics_fwd_kernel(int H, int W, int C, c
                                                           float* __restrict__ gt_out, float* __restrict__ part) {
     __shared__ float s_x[kReg][kReg + 1], s_y[kReg][kReg + 1];
     __shared__ float s_h[5][kReg][kLT + 1];
-    __shared__ float s_red[kMetricParts][4];
     const LossTile lt = loss_tile();
     const int c = lt.c;
     const int x0 = lt.bx * kLT, y0 = lt.by * kLT;
@@ -740,144 +543,267 @@ __global__ __launch_bounds__(256) void metrics_fwd_kernel(int H, int W, int C, c
         s_y[ry][rx] = yv;
     }
     __syncthreads();
-    // rows, then columns: the loss forward's filters (fused multiply-adds: SSIM is compared with a tolerance)
-    for (int i = tid; i < kReg * kLT; i += 256) {
-#pragma clang fp contract(fast)
-        const int ry = i / kLT, cx = i % kLT;
-        float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
-#pragma unroll
-        for (int k = 0; k < kWin; ++k) {
-            const float xv = s_x[ry][cx + k], yv = s_y[ry][cx + k];
-            a += win.w[k] * xv;
-            b += win.w[k] * yv;
-            aa += win.w[k] * (xv * xv);
-            bb += win.w[k] * (yv * yv);
-            ab += win.w[k] * (xv * yv);
-        }
-        s_h[0][ry][cx] = a;
-        s_h[1][ry][cx] = b;
-        s_h[2][ry][cx] = aa;
-        s_h[3][ry][cx] = bb;
-        s_h[4][ry][cx] = ab;
-    }
+    ssim_rows(win, s_x, s_y, s_h);
     __syncthreads();
     const int cy = tid >> 4, cx = tid & 15;
     const int py = y0 + cy, px = x0 + cx;
-    float ssum = 0.f;
+    float sums[kMetricParts] = {0.f, mse, mse_raw};
     if (py < Hv && px < Wv) {
-#pragma clang fp contract(fast)
-        float q[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < kWin; ++k)
-#pragma unroll
-            for (int m = 0; m < 5; ++m) q[m] += win.w[k] * s_h[m][cy + k][cx];
-        const float mu1 = q[0], mu2 = q[1];
-        const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu1_mu2 = mu1 * mu2;
-        const float s11 = q[2] - mu1_sq, s22 = q[3] - mu2_sq, s12 = q[4] - mu1_mu2;
-        const float A = 2.0f * mu1_mu2 + kC1, B = 2.0f * s12 + kC2;
-        const float Cc = mu1_sq + mu2_sq + kC1, D = s11 + s22 + kC2;
-        ssum = (A / Cc) * (B / D);
+        float q[5];
+        ssim_columns(win, s_h, cy, cx, q);
+        sums[0] = ssim_point(q).s;
     }
-    // workgroup sums (fixed order: wave reduce, then the 4 waves in order)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        ssum += __shfl_xor(ssum, off, 64);
-        mse += __shfl_xor(mse, off, 64);
-        mse_raw += __shfl_xor(mse_raw, off, 64);
-    }
-    if ((tid & 63) == 0) {
-        s_red[0][tid >> 6] = ssum;
-        s_red[1][tid >> 6] = mse;
-        s_red[2][tid >> 6] = mse_raw;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const int b = (lt.c * gridDim.y + lt.by) * gridDim.x + lt.bx;  // tile index: fixed reduction order
-#pragma unroll
-        for (int m = 0; m < kMetricParts; ++m)
-            part[kMetricParts * b + m] = ((s_red[m][0] + s_red[m][1]) + s_red[m][2]) + s_red[m][3];
-    }
-}
-
-// metrics = {PSNR, SSIM, MSE, MSE_raw}; PSNR = -10 log10(MSE) (+inf when every byte equals its target)
-__global__ __launch_bounds__(1024) void metrics_reduce_kernel(int nparts, const float* __restrict__ part,
-                                                              double inv_n1, double inv_np,
-                                                              float* __restrict__ metrics) {
-    __shared__ double s_s[1024], s_m[1024], s_r[1024];
-    double a = 0.0, m = 0.0, r = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 1024) {
-        a += (double)part[kMetricParts * i];
-        m += (double)part[kMetricParts * i + 1];
-        r += (double)part[kMetricParts * i + 2];
-    }
-    s_s[threadIdx.x] = a;
-    s_m[threadIdx.x] = m;
-    s_r[threadIdx.x] = r;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            s_s[threadIdx.x] += s_s[threadIdx.x + o];
-            s_m[threadIdx.x] += s_m[threadIdx.x + o];
-            s_r[threadIdx.x] += s_r[threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const float mse = (float)(s_m[0] * inv_n1);
-        metrics[0] = -10.0f * log10f(mse);
-        metrics[1] = (float)(s_s[0] * inv_np);
-        metrics[2] = mse;
-        metrics[3] = (float)(s_r[0] * inv_n1);
-    }
-}
-
-template <int DT, int CH>
-void launch_metrics(const FwdLaunch& a, unsigned char* rgb_u8_out) {
-    metrics_fwd_kernel<DT, CH><<<a.grid, 256, 0, a.st>>>(a.H, a.W, a.C, a.img, a.tex, a.alpha, a.bg, (GtPtr<DT>)a.gt,
-                                                         a.win, a.rgb_out, rgb_u8_out, a.gt_out, a.part);
+    block_sums<kMetricParts>(sums, lt, part);
 }
 
 }  // namespace
 
-// workspace: the forward's per-workgroup partial records, nothing else
-extern "C" size_t gstex_eval_metrics_workspace_size(int32_t H, int32_t W) {
-    if (H <= kHalo || W <= kHalo) return 0;
-    dim3 g;
-    return (size_t)loss_grid(H, W, g) * kMetricParts * sizeof(float);
+using namespace gstex;
+
+// forward: one workgroup per (tile, channel); backward: one per tile (its three channels in turn)
+static dim3 loss_grid(int H, int W, int channels = 3) {
+    return dim3((unsigned)((W + kLT - 1) / kLT), (unsigned)((H + kLT - 1) / kLT), (unsigned)channels);
 }
 
+// the forward's workgroups = its partial records
+static int loss_nparts(int H, int W) {
+    const dim3 g = loss_grid(H, W);
+    return (int)(g.x * g.y * g.z);
+}
+
+// workspace: the forward's partial records (part_floats each), padded to 256 bytes, then the gmaps
+static size_t loss_parts_bytes(int H, int W, int part_floats) {
+    return ((size_t)loss_nparts(H, W) * part_floats * sizeof(float) + 255) & ~(size_t)255;
+}
+
+static size_t loss_ws_size(int H, int W, int part_floats) {
+    if (H <= kHalo || W <= kHalo) return 0;
+    return loss_parts_bytes(H, W, part_floats) + (size_t)3 * 3 * (H - kHalo) * (W - kHalo) * sizeof(float);
+}
+
+extern "C" size_t gstex_loss_workspace_size(int32_t H, int32_t W) { return loss_ws_size(H, W, 2); }
+
+extern "C" size_t gstex_loss_target_workspace_size(int32_t H, int32_t W) { return loss_ws_size(H, W, 3); }
+
+// the partial records, nothing else (no gmaps)
+extern "C" size_t gstex_eval_metrics_workspace_size(int32_t H, int32_t W) {
+    if (H <= kHalo || W <= kHalo) return 0;
+    return (size_t)loss_nparts(H, W) * kMetricParts * sizeof(float);
+}
+
+namespace {
+
+// The checks every entry point makes, in the order they are reported.  `dims`: the message names the size (the
+// forwards); `pointers`: the entry point's own non-null test; `need`: its workspace size.
+int loss_check(const char* fn, bool dims, int H, int W, int C, bool pointers, const void* ws, size_t ws_bytes,
+               size_t need) {
+    const bool fits = H > kHalo && W > kHalo;
+    if (dims) GSTEX_REQUIRE(fits, "%s: image must be larger than the %d-tap window (%dx%d)", fn, kWin, H, W);
+    else GSTEX_REQUIRE(fits, "%s: image must be larger than the %d-tap window", fn, kWin);
+    GSTEX_REQUIRE(C >= 3 && C <= 8, "%s: tex channels must be in [3, 8] (got %d)", fn, C);
+    GSTEX_REQUIRE(pointers, "%s: null pointer", fn);
+    GSTEX_REQUIRE(ws && ws_bytes >= need, "%s: workspace too small", fn);
+    return GSTEX_OK;
+}
+
+// What the launches of every entry point take: the inputs, the workspace's two regions, and the scale factors of the
+// reduction (inv_*, w_*) and of the backward (k_*).
+struct LossLaunch {
+    hipStream_t st;
+    int H, W, C;
+    const float *img, *tex, *alpha, *bg;
+    const void *gt, *mask;
+    Win win;
+    float *part, *gmaps;
+    double inv_n1, inv_np;  // 1 / (3 H W), 1 / (3 (H - 10) (W - 10))
+    float w_l1, w_ssim;     // L = w_l1 L1 + w_ssim (1 - SSIM)
+    float k_l1, k_ssim;     // w_l1 / (3 H W), w_ssim / (3 (H - 10) (W - 10))
+};
+
+LossLaunch loss_launch(int H, int W, int C, const float* img, const float* tex, const float* alpha, const float* bg,
+                       const void* gt, const void* mask, const float* window, float ssim_lambda, void* workspace,
+                       int part_floats, void* stream) {
+    LossLaunch a;
+    a.st = as_stream(stream);
+    a.H = H, a.W = W, a.C = C;
+    a.img = img, a.tex = tex, a.alpha = alpha, a.bg = bg;
+    a.gt = gt, a.mask = mask;
+    for (int k = 0; k < kWin; ++k) a.win.w[k] = window[k];  // host array
+    a.part = (float*)workspace;
+    a.gmaps = (float*)((char*)workspace + loss_parts_bytes(H, W, part_floats));
+    a.inv_n1 = 1.0 / (3.0 * H * W);
+    a.inv_np = 1.0 / (3.0 * (H - kHalo) * (W - kHalo));
+    a.w_l1 = 1.0f - ssim_lambda, a.w_ssim = ssim_lambda;
+    a.k_l1 = (float)((1.0 - ssim_lambda) / (3.0 * H * W));
+    a.k_ssim = (float)(ssim_lambda / (3.0 * (H - kHalo) * (W - kHalo)));
+    return a;
+}
+
+// what only one kind of launch takes
+struct FwdOut {
+    float *rgb_out, *gt_out;
+};
+struct BwdArgs {
+    const float* grad_loss;
+    float *d_img, *d_tex, *d_alpha;
+};
+struct MetricsOut {
+    float* rgb_out;
+    unsigned char* rgb_u8_out;
+    float* gt_out;
+};
+
+template <int DT, int CH, int MK, bool EXT = true>
+void launch(const LossLaunch& a, const FwdOut& o) {
+    FwdExtra<EXT> ex;
+    if constexpr (EXT) ex = FwdExtra<true>{a.mask, o.gt_out};
+    loss_fwd_kernel<DT, CH, MK, EXT><<<loss_grid(a.H, a.W), 256, 0, a.st>>>(
+        a.H, a.W, a.C, a.img, a.tex, a.alpha, a.bg, (GtPtr<DT>)a.gt, a.win, o.rgb_out, a.gmaps, a.part, ex);
+}
+
+template <int DT, int CH, int MK>
+void launch(const LossLaunch& a, const BwdArgs& o) {
+    BwdExtra<MK> ex;
+    if constexpr (MK != kMaskNone) ex.mask = a.mask;
+    loss_bwd_kernel<DT, CH, MK><<<loss_grid(a.H, a.W, 1), 256, 0, a.st>>>(
+        a.H, a.W, a.C, a.img, a.tex, a.alpha, a.bg, (GtPtr<DT>)a.gt, a.win, a.gmaps, o.grad_loss, a.k_l1, a.k_ssim,
+        o.d_img, o.d_tex, o.d_alpha, ex);
+}
+
+template <int DT, int CH, int MK>  // (MK: always kMaskNone, gstex_eval_metrics refuses a mask)
+void launch(const LossLaunch& a, const MetricsOut& o) {
+    metrics_fwd_kernel<DT, CH><<<loss_grid(a.H, a.W), 256, 0, a.st>>>(
+        a.H, a.W, a.C, a.img, a.tex, a.alpha, a.bg, (GtPtr<DT>)a.gt, a.win, o.rgb_out, o.rgb_u8_out, o.gt_out, a.part);
+}
+
+// the forward's partial records -> the output floats
+template <int N, class Finish>
+void launch_reduce(const LossLaunch& a, const Finish& finish, float* out) {
+    reduce_kernel<N, Finish><<<1, 1024, 0, a.st>>>(loss_nparts(a.H, a.W), a.part, finish, out);
+}
+
+template <int DT, int CH, class Op>
+void dispatch_mask(int mk, const LossLaunch& a, const Op& o) {
+    if (mk == kMaskNone) launch<DT, CH, kMaskNone>(a, o);
+    else if (mk == kMaskF32) launch<DT, CH, kMaskF32>(a, o);
+    else launch<DT, CH, kMaskBool>(a, o);
+}
+
+// the policy instantiation of a (validated) target descriptor
+template <class Op>
+void dispatch_target(const gstex_loss_target& t, const LossLaunch& a, const Op& o) {
+    const int mk = !t.mask ? kMaskNone : (t.mask_dtype == GSTEX_MASK_BOOL ? kMaskBool : kMaskF32);
+    if (t.gt_dtype == GSTEX_GT_U8) {
+        if (t.gt_channels == 4) dispatch_mask<GSTEX_GT_U8, 4>(mk, a, o);
+        else dispatch_mask<GSTEX_GT_U8, 3>(mk, a, o);
+    } else {
+        if (t.gt_channels == 4) dispatch_mask<GSTEX_GT_F32, 4>(mk, a, o);
+        else dispatch_mask<GSTEX_GT_F32, 3>(mk, a, o);
+    }
+}
+
+// 0, or the message of the first invalid field (nothing is launched for an invalid descriptor)
+const char* target_error(const gstex_loss_target* t) {
+    if (!t) return "null target";
+    if (!t->gt) return "null target gt";
+    if (t->gt_dtype != GSTEX_GT_F32 && t->gt_dtype != GSTEX_GT_U8) return "gt_dtype out of range";
+    if (t->gt_channels != 3 && t->gt_channels != 4) return "gt_channels must be 3 or 4";
+    if (t->mask && t->mask_dtype != GSTEX_MASK_F32 && t->mask_dtype != GSTEX_MASK_BOOL)
+        return "mask_dtype out of range";
+    if (t->reserved != 0) return "reserved must be 0";
+    // an RGBA pixel is read as one word / one float4; fp32 values and masks as floats
+    const size_t align = t->gt_dtype == GSTEX_GT_F32 ? (t->gt_channels == 4 ? 16 : 4) : (t->gt_channels == 4 ? 4 : 1);
+    if ((uintptr_t)t->gt % align != 0) return "target gt is not aligned to its pixel load";
+    if (t->mask && t->mask_dtype == GSTEX_MASK_F32 && (uintptr_t)t->mask % 4 != 0) return "mask is not aligned";
+    return nullptr;
+}
+
+}  // namespace
+
+// gstex_loss_fwd / _bwd: the fp32, three-channel, unmasked instantiation without the MSE partial
+extern "C" int gstex_loss_fwd(int32_t H, int32_t W, int32_t C, const float* img, const float* tex,
+                              const float* alpha, const float* background, const float* gt, const float* window,
+                              float ssim_lambda, float* rgb_out, float* loss_out, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    const char* fn = "gstex_loss_fwd";
+    if (int rc = loss_check(fn, true, H, W, C, img && tex && alpha && background && gt && window && loss_out,
+                            workspace, workspace_bytes, gstex_loss_workspace_size(H, W)))
+        return rc;
+    const LossLaunch a = loss_launch(H, W, C, img, tex, alpha, background, gt, nullptr, window, ssim_lambda, workspace,
+                                     2, stream);
+    launch<GSTEX_GT_F32, 3, kMaskNone, false>(a, FwdOut{rgb_out, nullptr});
+    launch_reduce<2>(a, LossFinish{a.inv_n1, a.inv_np, a.w_l1, a.w_ssim}, loss_out);
+    return launch_status(fn);
+}
+
+extern "C" int gstex_loss_bwd(int32_t H, int32_t W, int32_t C, const float* img, const float* tex,
+                              const float* alpha, const float* background, const float* gt, const float* window,
+                              float ssim_lambda, const float* grad_loss, float* d_img, float* d_tex, float* d_alpha,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "gstex_loss_bwd";
+    if (int rc = loss_check(fn, false, H, W, C,
+                            img && tex && alpha && background && gt && window && grad_loss && d_img && d_tex && d_alpha,
+                            workspace, workspace_bytes, gstex_loss_workspace_size(H, W)))
+        return rc;
+    const LossLaunch a = loss_launch(H, W, C, img, tex, alpha, background, gt, nullptr, window, ssim_lambda, workspace,
+                                     2, stream);
+    launch<GSTEX_GT_F32, 3, kMaskNone>(a, BwdArgs{grad_loss, d_img, d_tex, d_alpha});
+    return launch_status(fn);
+}
+
+// ---- dataset targets (uint8 / RGBA / mask) ---------------------------------------------------------------------
+extern "C" int gstex_loss_target_fwd(int32_t H, int32_t W, int32_t C, const float* img, const float* tex,
+                                     const float* alpha, const float* background, const gstex_loss_target* target,
+                                     const float* window, float ssim_lambda, float* rgb_out, float* gt_out,
+                                     float* terms_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "gstex_loss_target_fwd";
+    const char* bad = target_error(target);
+    GSTEX_REQUIRE(!bad, "%s: %s", fn, bad);
+    if (int rc = loss_check(fn, true, H, W, C, img && tex && alpha && background && window && terms_out, workspace,
+                            workspace_bytes, gstex_loss_target_workspace_size(H, W)))
+        return rc;
+    const LossLaunch a = loss_launch(H, W, C, img, tex, alpha, background, target->gt, target->mask, window,
+                                     ssim_lambda, workspace, 3, stream);
+    dispatch_target(*target, a, FwdOut{rgb_out, gt_out});
+    launch_reduce<3>(a, LossFinish{a.inv_n1, a.inv_np, a.w_l1, a.w_ssim}, terms_out);
+    return launch_status(fn);
+}
+
+extern "C" int gstex_loss_target_bwd(int32_t H, int32_t W, int32_t C, const float* img, const float* tex,
+                                     const float* alpha, const float* background, const gstex_loss_target* target,
+                                     const float* window, float ssim_lambda, const float* grad_loss, float* d_img,
+                                     float* d_tex, float* d_alpha, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    const char* fn = "gstex_loss_target_bwd";
+    const char* bad = target_error(target);
+    GSTEX_REQUIRE(!bad, "%s: %s", fn, bad);
+    if (int rc = loss_check(fn, false, H, W, C,
+                            img && tex && alpha && background && window && grad_loss && d_img && d_tex && d_alpha,
+                            workspace, workspace_bytes, gstex_loss_target_workspace_size(H, W)))
+        return rc;
+    const LossLaunch a = loss_launch(H, W, C, img, tex, alpha, background, target->gt, target->mask, window,
+                                     ssim_lambda, workspace, 3, stream);
+    dispatch_target(*target, a, BwdArgs{grad_loss, d_img, d_tex, d_alpha});
+    return launch_status(fn);
+}
+
+// ---- evaluation metrics ----------------------------------------------------------------------------------------
 extern "C" int gstex_eval_metrics(int32_t H, int32_t W, int32_t C, const float* img, const float* tex,
                                   const float* alpha, const float* background, const gstex_loss_target* target,
                                   const float* window, float* rgb_out, uint8_t* rgb_u8_out, float* gt_out,
                                   float* metrics_out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "gstex_eval_metrics";
     // the reference's evaluation applies no mask: a descriptor that carries one is a caller's mistake, not ignored
     const char* bad = target && target->gt && target->mask ? "a mask is not supported (the evaluation applies none)"
                                                            : target_error(target);
-    GSTEX_REQUIRE(!bad, "gstex_eval_metrics: %s", bad);
-    GSTEX_REQUIRE(H > kHalo && W > kHalo, "gstex_eval_metrics: image must be larger than the %d-tap window (%dx%d)",
-                  kWin, H, W);
-    GSTEX_REQUIRE(C >= 3 && C <= 8, "gstex_eval_metrics: tex channels must be in [3, 8] (got %d)", C);
-    GSTEX_REQUIRE(img && tex && alpha && background && window && metrics_out, "gstex_eval_metrics: null pointer");
-    GSTEX_REQUIRE(workspace && workspace_bytes >= gstex_eval_metrics_workspace_size(H, W),
-                  "gstex_eval_metrics: workspace too small");
-    FwdLaunch a;
-    a.st = as_stream(stream);
-    a.H = H, a.W = W, a.C = C;
-    a.img = img, a.tex = tex, a.alpha = alpha, a.bg = background;
-    a.gt = target->gt, a.mask = nullptr;
-    for (int k = 0; k < kWin; ++k) a.win.w[k] = window[k];  // host array
-    a.rgb_out = rgb_out, a.gt_out = gt_out;
-    a.gmaps = nullptr;
-    a.part = (float*)workspace;
-    const int nparts = loss_grid(H, W, a.grid);
-    if (target->gt_dtype == GSTEX_GT_U8) {
-        if (target->gt_channels == 4) launch_metrics<GSTEX_GT_U8, 4>(a, rgb_u8_out);
-        else launch_metrics<GSTEX_GT_U8, 3>(a, rgb_u8_out);
-    } else {
-        if (target->gt_channels == 4) launch_metrics<GSTEX_GT_F32, 4>(a, rgb_u8_out);
-        else launch_metrics<GSTEX_GT_F32, 3>(a, rgb_u8_out);
-    }
-    metrics_reduce_kernel<<<1, 1024, 0, a.st>>>(nparts, a.part, 1.0 / (3.0 * H * W),
-                                                1.0 / (3.0 * (H - kHalo) * (W - kHalo)), metrics_out);
-    return launch_status("gstex_eval_metrics");
+    GSTEX_REQUIRE(!bad, "%s: %s", fn, bad);
+    if (int rc = loss_check(fn, true, H, W, C, img && tex && alpha && background && window && metrics_out, workspace,
+                            workspace_bytes, gstex_eval_metrics_workspace_size(H, W)))
+        return rc;
+    LossLaunch a = loss_launch(H, W, C, img, tex, alpha, background, target->gt, nullptr, window, 0.0f, workspace,
+                               kMetricParts, stream);
+    a.gmaps = nullptr;  // its workspace ends with the partial records
+    dispatch_target(*target, a, MetricsOut{rgb_out, rgb_u8_out, gt_out});
+    launch_reduce<kMetricParts>(a, MetricsFinish{a.inv_n1, a.inv_np}, metrics_out);
+    return launch_status(fn);
 }

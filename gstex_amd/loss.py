@@ -48,54 +48,99 @@ def gaussian_window(size: int = 11, sigma: float = 1.5) -> torch.Tensor:
     return w
 
 
-def _check(img, tex, alpha, background, gt):
+def _check_args(fn, img, tex, alpha, background, image, mask=None, gt=False):
+    """The arguments of photometric_loss, image_loss and image_metrics.  Shapes and dtypes first, then the window, then
+    the device: each refusal names what is wrong with the call.  gt: `image` is photometric_loss's gt, float32
+    (H, W, 3) like the render.  Returns the mask as (H, W) (or None)."""
+    if alpha.dim() != 2:
+        raise ValueError(f"{fn}: alpha must be a CUDA fp32 tensor of shape (H, W)")
     H, W = alpha.shape
-    for name, t, shape in (("img", img, (H, W, 3)), ("alpha", alpha, (H, W)), ("gt", gt, (H, W, 3)),
-                           ("background", background, (3,))):
-        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_cuda:
-            raise ValueError(f"photometric_loss: {name} must be a CUDA fp32 tensor of shape {shape}")
+    fp32 = [("img", img, (H, W, 3)), ("alpha", alpha, (H, W)), ("background", background, (3,))]
+    if gt:
+        fp32.insert(2, ("gt", image, (H, W, 3)))
+    for name, t, shape in fp32:
+        if tuple(t.shape) != shape or t.dtype != torch.float32:
+            raise ValueError(f"{fn}: {name} must be a CUDA fp32 tensor of shape {shape}")
     if tex.dim() != 3 or tuple(tex.shape[:2]) != (H, W) or not 3 <= tex.shape[2] <= 8 or tex.dtype != torch.float32:
-        raise ValueError("photometric_loss: tex must be CUDA fp32 (H, W, C) with 3 <= C <= 8")
+        raise ValueError(f"{fn}: tex must be CUDA fp32 (H, W, C) with 3 <= C <= 8")
+    if not gt:
+        mask = _check_target(fn, alpha, image, mask)
     if H <= 10 or W <= 10:
-        raise ValueError("photometric_loss: the image must be larger than the 11-tap SSIM window")
+        raise ValueError(f"{fn}: the image must be larger than the 11-tap SSIM window")
+    for name, t in (("img", img), ("tex", tex), ("alpha", alpha), ("background", background),
+                    ("gt" if gt else "image", image), ("mask", mask)):
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{fn}: {name} must be a CUDA tensor")
+    return mask
+
+
+def _aligned(t: torch.Tensor, nbytes: int) -> torch.Tensor:
+    """t, or a fresh copy when its storage offset breaks the kernels' pixel load (an RGBA pixel is one load)."""
+    return t if t.data_ptr() % nbytes == 0 else t.clone()
+
+
+def _prepare(ws_size, img, tex, alpha, background, image, mask=None, image_align=16):
+    """What the kernels read: the tensors detached and contiguous, the image and the mask aligned to their loads; and
+    the workspace of the size the library's function `ws_size` gives."""
+    img, tex, alpha, background = (t.detach().contiguous() for t in (img, tex, alpha, background))
+    image = _aligned(image.detach().contiguous(), image_align)
+    if mask is not None:
+        mask = _aligned(mask.detach().contiguous(), 4)
+    H, W = alpha.shape
+    ws = torch.empty((int(getattr(_lib.load(), ws_size)(H, W)),), device=img.device, dtype=torch.uint8)
+    return img, tex, alpha, background, image, mask, ws
+
+
+def _loss_target(image, mask) -> _lib.GstexLossTarget:
+    return _lib.GstexLossTarget(
+        ptr(image), ptr(mask), _lib.GT_U8 if image.dtype == torch.uint8 else _lib.GT_F32, int(image.shape[2]),
+        _lib.MASK_BOOL if mask is not None and mask.dtype == torch.bool else _lib.MASK_F32, 0)
+
+
+def _backward(ctx, g_loss, n_inputs):
+    """The backward of both autograd functions: forward saved (img, tex, alpha, background, target, ws[, mask]) and
+    set ctx.ssim_lambda and ctx.dataset_target (gstex_loss_target_bwd takes the target as a descriptor)."""
+    if g_loss is None:
+        return (None,) * n_inputs
+    img, tex, alpha, background, image, ws, *rest = ctx.saved_tensors
+    H, W = alpha.shape
+    C = tex.shape[2]
+    d_img = torch.empty_like(img)
+    d_tex = torch.empty_like(tex)
+    d_alpha = torch.empty_like(alpha)
+    g = g_loss.detach().to(torch.float32).contiguous()
+    if ctx.dataset_target:
+        target = _loss_target(image, rest[0] if rest else None)
+        symbol, gt = "gstex_loss_target_bwd", ctypes.byref(target)
+    else:
+        symbol, gt = "gstex_loss_bwd", ptr(image)
+    call(symbol, H, W, C, ptr(img), ptr(tex), ptr(alpha), ptr(background), gt, _cwin(), ctx.ssim_lambda, g.data_ptr(),
+         ptr(d_img), ptr(d_tex), ptr(d_alpha), ptr(ws), ws.numel(), _lib.stream_of(img.device))
+    return (d_img, d_tex, d_alpha) + (None,) * (n_inputs - 3)
 
 
 class _PhotometricLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, tex, alpha, background, gt, ssim_lambda):
-        _check(img, tex, alpha, background, gt)
-        img, tex, alpha, background, gt = (t.detach().contiguous() for t in (img, tex, alpha, background, gt))
+        _check_args("photometric_loss", img, tex, alpha, background, gt, gt=True)
+        img, tex, alpha, background, gt, _, ws = _prepare("gstex_loss_workspace_size", img, tex, alpha, background, gt,
+                                                          image_align=4)
         H, W = alpha.shape
         C = tex.shape[2]
-        cwin = _cwin()
-        ws = torch.empty((int(_lib.load().gstex_loss_workspace_size(H, W)),), device=img.device, dtype=torch.uint8)
         out = torch.empty((3,), device=img.device, dtype=torch.float32)
         rgb = torch.empty((H, W, 3), device=img.device, dtype=torch.float32)
-        st = _lib.stream_of(img.device)
-        call("gstex_loss_fwd", H, W, C, ptr(img), ptr(tex), ptr(alpha), ptr(background), ptr(gt), cwin,
-             float(ssim_lambda), ptr(rgb), ptr(out), ptr(ws), ws.numel(), st)
+        call("gstex_loss_fwd", H, W, C, ptr(img), ptr(tex), ptr(alpha), ptr(background), ptr(gt), _cwin(),
+             float(ssim_lambda), ptr(rgb), ptr(out), ptr(ws), ws.numel(), _lib.stream_of(img.device))
         ctx.save_for_backward(img, tex, alpha, background, gt, ws)
         ctx.ssim_lambda = float(ssim_lambda)
+        ctx.dataset_target = False
         ctx.mark_non_differentiable(rgb)
         ctx.set_materialize_grads(False)  # rgb's (always unused) gradient stays None, no zero image
         return out[0], rgb  # out[1:] = (L1, SSIM) stay readable through the base tensor
 
     @staticmethod
     def backward(ctx, g_loss, g_rgb):
-        if g_loss is None:
-            return None, None, None, None, None, None
-        img, tex, alpha, background, gt, ws = ctx.saved_tensors
-        H, W = alpha.shape
-        C = tex.shape[2]
-        cwin = _cwin()
-        d_img = torch.empty_like(img)
-        d_tex = torch.empty_like(tex)
-        d_alpha = torch.empty_like(alpha)
-        g = g_loss.detach().to(torch.float32).contiguous()
-        call("gstex_loss_bwd", H, W, C, ptr(img), ptr(tex), ptr(alpha), ptr(background), ptr(gt), cwin,
-             ctx.ssim_lambda, g.data_ptr(), ptr(d_img), ptr(d_tex), ptr(d_alpha), ptr(ws), ws.numel(),
-             _lib.stream_of(img.device))
-        return d_img, d_tex, d_alpha, None, None, None
+        return _backward(ctx, g_loss, 6)
 
 
 def photometric_loss(img, tex, alpha, background, gt, ssim_lambda: float = 0.2):
@@ -139,80 +184,32 @@ def _check_target(name, alpha, image, mask):
     return mask
 
 
-def _check_image(img, tex, alpha, background, image, mask, fn="image_loss"):
-    """Shapes and dtypes first, then the window, then the device: each refusal names what is wrong with the call."""
-    if alpha.dim() != 2:
-        raise ValueError(f"{fn}: alpha must be a CUDA fp32 tensor of shape (H, W)")
-    H, W = alpha.shape
-    for name, t, shape in (("img", img, (H, W, 3)), ("alpha", alpha, (H, W)), ("background", background, (3,))):
-        if tuple(t.shape) != shape or t.dtype != torch.float32:
-            raise ValueError(f"{fn}: {name} must be a CUDA fp32 tensor of shape {shape}")
-    if tex.dim() != 3 or tuple(tex.shape[:2]) != (H, W) or not 3 <= tex.shape[2] <= 8 or tex.dtype != torch.float32:
-        raise ValueError(f"{fn}: tex must be CUDA fp32 (H, W, C) with 3 <= C <= 8")
-    mask = _check_target(fn, alpha, image, mask)
-    if H <= 10 or W <= 10:
-        raise ValueError(f"{fn}: the image must be larger than the 11-tap SSIM window")
-    for name, t in (("img", img), ("tex", tex), ("alpha", alpha), ("background", background), ("image", image),
-                    ("mask", mask)):
-        if t is not None and not t.is_cuda:
-            raise ValueError(f"{fn}: {name} must be a CUDA tensor")
-    return mask
-
-
-def _aligned(t: torch.Tensor, nbytes: int) -> torch.Tensor:
-    """t, or a fresh copy when its storage offset breaks the kernels' pixel load (an RGBA pixel is one load)."""
-    return t if t.data_ptr() % nbytes == 0 else t.clone()
-
-
-def _loss_target(image, mask) -> _lib.GstexLossTarget:
-    return _lib.GstexLossTarget(
-        ptr(image), ptr(mask), _lib.GT_U8 if image.dtype == torch.uint8 else _lib.GT_F32, int(image.shape[2]),
-        _lib.MASK_BOOL if mask is not None and mask.dtype == torch.bool else _lib.MASK_F32, 0)
-
-
 class _ImageLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, tex, alpha, background, image, mask, ssim_lambda):
-        mask = _check_image(img, tex, alpha, background, image, mask)
-        img, tex, alpha, background = (t.detach().contiguous() for t in (img, tex, alpha, background))
-        image = _aligned(image.detach().contiguous(), 16)
-        if mask is not None:
-            mask = _aligned(mask.detach().contiguous(), 4)
+        mask = _check_args("image_loss", img, tex, alpha, background, image, mask)
+        img, tex, alpha, background, image, mask, ws = _prepare("gstex_loss_target_workspace_size", img, tex, alpha,
+                                                                background, image, mask)
         H, W = alpha.shape
         C = tex.shape[2]
-        cwin = _cwin()
         dev = img.device
-        ws = torch.empty((int(_lib.load().gstex_loss_target_workspace_size(H, W)),), device=dev, dtype=torch.uint8)
         terms = torch.empty((4,), device=dev, dtype=torch.float32)
         rgb = torch.empty((H, W, 3), device=dev, dtype=torch.float32)
         gt = torch.empty((H, W, 3), device=dev, dtype=torch.float32)
         target = _loss_target(image, mask)
         call("gstex_loss_target_fwd", H, W, C, ptr(img), ptr(tex), ptr(alpha), ptr(background), ctypes.byref(target),
-             cwin, float(ssim_lambda), ptr(rgb), ptr(gt), ptr(terms), ptr(ws), ws.numel(), _lib.stream_of(dev))
+             _cwin(), float(ssim_lambda), ptr(rgb), ptr(gt), ptr(terms), ptr(ws), ws.numel(), _lib.stream_of(dev))
         saved = (img, tex, alpha, background, image, ws) + ((mask,) if mask is not None else ())
         ctx.save_for_backward(*saved)
         ctx.ssim_lambda = float(ssim_lambda)
+        ctx.dataset_target = True
         ctx.mark_non_differentiable(rgb, gt, terms)
         ctx.set_materialize_grads(False)
         return terms[0], rgb, gt, terms
 
     @staticmethod
     def backward(ctx, g_loss, g_rgb, g_gt, g_terms):
-        if g_loss is None:
-            return (None,) * 7
-        img, tex, alpha, background, image, ws, *rest = ctx.saved_tensors
-        mask = rest[0] if rest else None
-        H, W = alpha.shape
-        C = tex.shape[2]
-        d_img = torch.empty_like(img)
-        d_tex = torch.empty_like(tex)
-        d_alpha = torch.empty_like(alpha)
-        g = g_loss.detach().to(torch.float32).contiguous()
-        target = _loss_target(image, mask)
-        call("gstex_loss_target_bwd", H, W, C, ptr(img), ptr(tex), ptr(alpha), ptr(background), ctypes.byref(target),
-             _cwin(), ctx.ssim_lambda, g.data_ptr(), ptr(d_img), ptr(d_tex), ptr(d_alpha), ptr(ws), ws.numel(),
-             _lib.stream_of(img.device))
-        return d_img, d_tex, d_alpha, None, None, None, None
+        return _backward(ctx, g_loss, 7)
 
 
 def image_loss(img, tex, alpha, background, image, mask=None, ssim_lambda: float = 0.2) -> ImageLoss:
@@ -225,6 +222,20 @@ def image_loss(img, tex, alpha, background, image, mask=None, ssim_lambda: float
     return ImageLoss(loss, rgb, gt, terms)
 
 
+def _target_eager(image, background):
+    """The (H, W, 3) float32 target of a dataset image with torch ops: get_gt_img's v / 255 and
+    composite_with_background (gstex.py:1244-1245, 1256-1258)."""
+    if image.dtype == torch.uint8:
+        # get_gt_img divides on the CPU, a true division.  A tensor divisor gives that on every device: by a Python
+        # scalar torch's device kernel multiplies by the rounded reciprocal instead, which is not the division the CPU
+        # data path (and the fused kernels) perform
+        image = image.float() / torch.full((), 255.0, device=image.device)
+    if image.shape[2] == 4:
+        a = image[..., -1].unsqueeze(-1).repeat((1, 1, 3))
+        return a * image[..., :3] + (1 - a) * background
+    return image
+
+
 def image_loss_eager(rgb, background, image, mask=None, ssim_lambda: float = 0.2) -> ImageLoss:
     """image_loss with torch ops on the composited render `rgb`, restating gstex.py:1244-1245, 1256-1258 and
     1294-1303 (runs on any device; the trainer's fused_loss=False path and the tests' reference)."""
@@ -233,15 +244,7 @@ def image_loss_eager(rgb, background, image, mask=None, ssim_lambda: float = 0.2
     if rgb.dim() != 3 or rgb.shape[2] != 3:
         raise ValueError("image_loss_eager: rgb must have shape (H, W, 3)")
     mask = _check_target("image_loss_eager", rgb[..., 0], image, mask)
-    if image.dtype == torch.uint8:
-        # a tensor divisor: by a Python scalar torch's device kernel multiplies by the rounded reciprocal instead,
-        # which is not the division the CPU data path (and the fused kernel) performs
-        image = image.float() / torch.full((), 255.0, device=image.device)
-    if image.shape[2] == 4:
-        a = image[..., -1].unsqueeze(-1).repeat((1, 1, 3))
-        gt = a * image[..., :3] + (1 - a) * background
-    else:
-        gt = image
+    gt = _target_eager(image, background)
     mse = torch.mean((rgb.detach() - gt) ** 2)
     x, y = gt, rgb
     if mask is not None:
@@ -303,15 +306,14 @@ def image_metrics(img, tex, alpha, background, image, out=None) -> ImageMetrics:
     tensor of 4 elements the metrics are written into (one row of a per-image table)."""
     fn = "image_metrics"
     _check_out(fn, out)
-    _check_image(img, tex, alpha, background, image, None, fn=fn)
+    _check_args(fn, img, tex, alpha, background, image)
     if out is not None and (not out.is_cuda or out.device != img.device):
         raise ValueError(f"{fn}: out must be a contiguous CUDA fp32 tensor of 4 elements on the images' device")
-    img, tex, alpha, background = (t.detach().contiguous() for t in (img, tex, alpha, background))
-    image = _aligned(image.detach().contiguous(), 16)
+    img, tex, alpha, background, image, _, ws = _prepare("gstex_eval_metrics_workspace_size", img, tex, alpha,
+                                                         background, image)
     H, W = alpha.shape
     C = tex.shape[2]
     dev = img.device
-    ws = torch.empty((int(_lib.load().gstex_eval_metrics_workspace_size(H, W)),), device=dev, dtype=torch.uint8)
     metrics = out if out is not None else torch.empty((4,), device=dev, dtype=torch.float32)
     rgb = torch.empty((H, W, 3), device=dev, dtype=torch.float32)
     rgb_u8 = torch.empty((H, W, 3), device=dev, dtype=torch.uint8)
@@ -334,15 +336,7 @@ def image_metrics_eager(rgb, background, image) -> ImageMetrics:
         raise ValueError("image_metrics_eager: rgb must have shape (H, W, 3)")
     _check_target("image_metrics_eager", rgb[..., 0], image, None)
     rgb = rgb.detach()
-    if image.dtype == torch.uint8:
-        # get_gt_img divides on the CPU, a true division: a tensor divisor gives that on every device (see
-        # image_loss_eager)
-        image = image.float() / torch.full((), 255.0, device=image.device)
-    if image.shape[2] == 4:
-        a = image[..., -1].unsqueeze(-1).repeat((1, 1, 3))
-        gt = a * image[..., :3] + (1 - a) * background
-    else:
-        gt = image
+    gt = _target_eager(image, background)
     gt_r = torch.moveaxis(gt, -1, 0)[None, ...]
     pred = torch.moveaxis(rgb, -1, 0)[None, ...]
     q = (255.0 * pred).to(dtype=torch.uint8)

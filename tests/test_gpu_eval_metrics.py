@@ -2,7 +2,10 @@
 restatement of the reference's protocol (image_metrics_eager), and GStexTrainer.evaluate / evaluate_split.
 
 Shapes: 37x45 (partial edge tiles; 3 x 3 tiles x 3 channels = 27 forward workgroups, so the XCD remap has a
-remainder) and 11x12 (1 x 2 valid SSIM positions).  SSIM and the MSEs carry the loss terms' tolerance of
+remainder) and 11x12 (1 x 2 valid SSIM positions); 300x290 (19 x 19 tiles x 3 channels = 1083 partial records, partial
+edge tiles on both axes) in one case, where the reduction's strided loop takes a second pass with a ragged tail: there
+the eager twin's own fp32 metrics lie within 2e-8 (PSNR: 3.3e-7) of their fp64 evaluation (on the CPU, this seed),
+well inside a quarter of the bounds below.  SSIM and the MSEs carry the loss terms' tolerance of
 test_image_loss_matches_eager (2e-6 * max(1, |want|)); PSNR = -10 log10(MSE) carries that bound propagated:
 10 / ln 10 = 4.343 times the MSE's relative tolerance, plus 2 fp32 ulps of the PSNR for log10f and the rounding."""
 import numpy as np
@@ -13,6 +16,7 @@ pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
 SHAPES = [(37, 45), (11, 12)]
+LARGE = (300, 290)
 TOL = 2e-6
 
 
@@ -73,10 +77,13 @@ def _check_metrics(got, want):
     assert abs(got[0] - want[0]) <= psnr_tol, f"PSNR: {got[0]!r} vs {want[0]!r} (tolerance {psnr_tol:.3e})"
 
 
-@pytest.mark.parametrize("channels", [3, 4])
-@pytest.mark.parametrize("dtype", ["f32", "u8"])
-@pytest.mark.parametrize("C", [3, 4])
-@pytest.mark.parametrize("shape", SHAPES)
+# the cross product over SHAPES (ids as a stack of parametrize decorators gives them), and LARGE once
+_EAGER_CASES = [pytest.param(shape, C, dtype, channels, id=f"shape{i}-{C}-{dtype}-{channels}")
+                for i, shape in enumerate(SHAPES) for C in (3, 4) for dtype in ("f32", "u8") for channels in (3, 4)]
+_EAGER_CASES.append(pytest.param(LARGE, 4, "u8", 4, id="300x290-4-u8-4"))
+
+
+@pytest.mark.parametrize("shape,C,dtype,channels", _EAGER_CASES)
 def test_image_metrics_matches_eager(shape, C, dtype, channels):
     from gstex_amd.loss import image_loss, image_metrics, image_metrics_eager
 

@@ -4,7 +4,10 @@ cases where it must reproduce photometric_loss bit for bit, and the trainer's st
 and a random background.
 
 Shapes: 37x45 (partial edge tiles; 3 x 3 tiles x 3 channels = 27 forward workgroups, so the XCD remap has a
-remainder) and 11x12 (1 x 2 valid SSIM positions).  Tolerances are those of test_fused_loss_matches_eager_torch."""
+remainder) and 11x12 (1 x 2 valid SSIM positions); 300x290 (19 x 19 tiles x 3 channels = 1083 partial records, partial
+edge tiles on both axes) in one case each, where the reduction's strided loop takes a second pass with a ragged tail.
+Tolerances are those of test_fused_loss_matches_eager_torch; at 300x290 the eager twin's own fp32 terms lie within
+2.1e-8 of their fp64 evaluation (on the CPU, this seed), well inside a quarter of the 2e-6 bound."""
 import pytest
 import torch
 
@@ -12,6 +15,7 @@ pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
 SHAPES = [(37, 45), (11, 12)]
+LARGE = (300, 290)
 
 
 def _raster_outputs(H, W, C, seed):
@@ -66,11 +70,14 @@ def _eager(leaves, bg, image, mask, upstream=1.7):
     return ref
 
 
-@pytest.mark.parametrize("mask_kind", ["none", "bool", "f32"])
-@pytest.mark.parametrize("channels", [3, 4])
-@pytest.mark.parametrize("dtype", ["f32", "u8"])
-@pytest.mark.parametrize("C", [3, 4])
-@pytest.mark.parametrize("shape", SHAPES)
+# the cross product over SHAPES (ids as a stack of parametrize decorators gives them), and LARGE once
+_EAGER_CASES = [pytest.param(shape, C, dtype, channels, mask_kind, id=f"shape{i}-{C}-{dtype}-{channels}-{mask_kind}")
+                for i, shape in enumerate(SHAPES) for C in (3, 4) for dtype in ("f32", "u8") for channels in (3, 4)
+                for mask_kind in ("none", "bool", "f32")]
+_EAGER_CASES.append(pytest.param(LARGE, 4, "u8", 4, "bool", id="300x290-4-u8-4-bool"))
+
+
+@pytest.mark.parametrize("shape,C,dtype,channels,mask_kind", _EAGER_CASES)
 def test_image_loss_matches_eager(shape, C, dtype, channels, mask_kind):
     from gstex_amd.loss import image_loss
 
@@ -107,11 +114,16 @@ def test_image_loss_matches_eager(shape, C, dtype, channels, mask_kind):
         assert float(leaves[0].grad[16:32, 16:32].abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("case", ["f32", "u8", "u8_rgba_opaque", "all_true_mask"])
-@pytest.mark.parametrize("shape", SHAPES)
+_SAME_BITS_CASES = [pytest.param(shape, case, id=f"shape{i}-{case}") for i, shape in enumerate(SHAPES)
+                    for case in ("f32", "u8", "u8_rgba_opaque", "all_true_mask")]
+_SAME_BITS_CASES.append(pytest.param(LARGE, "f32", id="300x290-f32"))
+
+
+@pytest.mark.parametrize("shape,case", _SAME_BITS_CASES)
 def test_image_loss_reproduces_photometric_loss(shape, case):
     """Where the target policy adds no arithmetic (or only multiplications by 1 and additions of 0), the template's
-    instantiations give photometric_loss's bits: rgb, the loss and the three gradients."""
+    instantiations give photometric_loss's bits: rgb, the loss and the three gradients.  (At 300x290 the two- and the
+    three-column reductions are compared over more than one pass of their strided loop.)"""
     from gstex_amd.loss import image_loss, photometric_loss
 
     H, W = shape
