@@ -129,6 +129,19 @@ class GstexLossTarget(ctypes.Structure):
                 ("mask_dtype", c_int32), ("reserved", c_int32)]
 
 
+class GstexPaintScatterArgs(ctypes.Structure):
+    """gstex_paint_scatter_args (added within ABI 19): a stroke scattered into the texel accumulator."""
+    _fields_ = [("cam", GstexCamera), ("settings", c_int32), ("stroke_dtype", c_int32), ("eps", c_float)] + [
+        (name, c_void_p) for name in ("records", "tile_ranges", "tile_order", "sorted_ids", "stroke", "depth")] + [
+        ("n_texels", c_int64), ("acc", c_void_p)]
+
+
+class GstexPaintBlendArgs(ctypes.Structure):
+    """gstex_paint_blend_args (added within ABI 19): the accumulator blended into the texels."""
+    _fields_ = [("n_texels", c_int64), ("acc", c_void_p), ("texture", c_void_p), ("scale", c_float),
+                ("shift", c_float)]
+
+
 GT_F32, GT_U8 = 0, 1  # GSTEX_GT_*
 MASK_F32, MASK_BOOL = 0, 1  # GSTEX_MASK_*
 ADAM_ZERO_GRAD = 1  # GSTEX_ADAM_ZERO_GRAD
@@ -182,6 +195,8 @@ SIGNATURES = {
     "gstex_sh_rest_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "gstex_sh_rest_bwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "gstex_texture_edit": (c_int32, [_CAM, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P]),
+    "gstex_paint_scatter": (c_int32, [POINTER(GstexPaintScatterArgs), _P]),
+    "gstex_paint_blend": (c_int32, [POINTER(GstexPaintBlendArgs), _P]),
     "gstex_loss_workspace_size": (c_size_t, [c_int32, c_int32]),
     "gstex_loss_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, POINTER(c_float), c_float, _P, _P,
                                  _P, c_size_t, _P]),

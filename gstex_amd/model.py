@@ -183,6 +183,10 @@ class GStexTrainer:
         self.texture_grad_ready = None
         self.texture_grad_route = None  # GradSync: the per-render texel-gradient target (several renders per step)
         self.test_colors = None  # eval-render test colours (gstex.py:309)
+        # paint(): the (n_texels, 5) stroke accumulator (zero between calls: the blend kernel re-zeroes what the
+        # scatter touched) and the per-splat scratch of its depth render
+        self._paint_acc = None
+        self._paint_scratch = {}
         # defer_texture (not in the reference; fused Adam on a HIP device): the texel parameter's Adam update of step k
         # (73 % of the parameters at cfg3) runs at step k+1's zero_grad() or render, before the raster forward, the first reader of
         # the texels -- at the pair-count read-back when there is one (the device runs it while the host waits), else
@@ -531,6 +535,89 @@ class GStexTrainer:
         return dict(psnr=float(mean[0]), ssim=float(mean[1]), mse=float(mean[2]), mse_raw=float(mean[3]),
                     gaussian_count=float(self.means.shape[0]), texel_count=float(self.n_texels),
                     per_image=per_image)
+
+    # ------------------------------------------------------------------ appearance editing
+    @torch.no_grad()
+    def paint(self, view: View, stroke: torch.Tensor, texture: torch.Tensor | None = None, depth_eps: float = 1e-2,
+              depth: torch.Tensor | None = None) -> torch.Tensor:
+        """draw_from_view (gstex.py:489-606): back-project a screen-space RGBA stroke -- (H, W, 4), float32 in [0, 1]
+        or uint8 (read as v / 255), straight alpha -- onto the texels of the surface the view sees.
+
+        One preprocess, one binning and one raster setup; one depth render (the trainer's settings, glob_scale 1);
+        then every pair whose hit depth lies within depth_eps of the rendered depth adds the stroke to its four
+        texels (ops.paint_scatter, settings 1 << 13 alone as gstex.py:599), and the sums are blended into the texels
+        (ops.paint_blend, gstex.py:603-605).  texture: a raster-space (n_texels, 3) float32 tensor on the trainer's
+        device, edited in place and returned; None: a fresh SH2RGB(texture_dc[:n_texels]).  depth: an (H, W) map used
+        instead of the depth render.  With no texels (2DGS mode) or a view that hits no tile the texture is returned
+        as it is.  No training state is touched (a pending deferred texel update is run first, as any reader of the
+        texels does): the result shows in eval_render(view, edit_texture=...), bake_edits() makes it permanent."""
+        return self._paint(view, stroke, texture, (1.0, 0.0), depth_eps, depth)
+
+    def _paint(self, view, stroke, texture, transform, depth_eps, depth):
+        self.wait_texture()
+        T, d = self.n_texels, self.means.device
+        if texture is None:
+            texture = SH2RGB(self.texture_dc.detach()[:T])
+        ops._check(isinstance(texture, torch.Tensor) and texture.dtype == torch.float32 and texture.device == d
+                   and texture.dim() == 2 and texture.shape[1] == 3 and texture.shape[0] >= T
+                   and texture.is_contiguous(),
+                   f"texture must be a contiguous float32 (>= {T}, 3) tensor on {d}")
+        H, W = int(view.H), int(view.W)
+        ops._check(isinstance(stroke, torch.Tensor) and stroke.dtype in (torch.float32, torch.uint8)
+                   and tuple(stroke.shape) == (H, W, 4) and stroke.device == d,
+                   f"stroke must be a float32 or uint8 ({H}, {W}, 4) tensor on {d}")
+        if depth is not None:
+            ops._check(depth.dtype == torch.float32 and tuple(depth.shape) == (H, W) and depth.device == d,
+                       f"depth must be a float32 ({H}, {W}) tensor on {d}")
+        if T == 0:
+            return texture
+        quats, scales, opacities, uv0, umap, vmap, _ = activate(
+            self.means, self.quats, self.scales, self.opacities, self.mappings, view.campos)
+        intr = (view.fx, view.fy, view.cx, view.cy)
+        depths, centers, extents, nth = ops.preprocess(self.means, scales, 1, quats, view.viewmat, intr, H, W)
+        bins = ops.bin_gaussians(centers, extents, depths, nth, H, W)
+        if bins.sorted_ids.shape[0] == 0:  # no splat reaches a tile
+            return texture
+        cam = (view.viewmat, view.c2w, view.fx, view.fy, view.cx, view.cy, H, W)
+        records, rendered = ops.depth_render(self.texture_dims, centers, nth, opacities, self.means.detach(), scales, 1,
+                                             quats, uv0, umap, vmap, *cam, self.settings, bins,
+                                             scratch=self._paint_scratch, render=depth is None)
+        acc = self._paint_acc
+        if acc is None or acc.shape[0] != T:  # (re-made when a rechart changes n_texels; zero from here on: the
+            acc = self._paint_acc = torch.zeros((T, 5), device=d, dtype=torch.float32)  # blend re-zeroes its rows)
+        ops.paint_scatter(acc, stroke, rendered if depth is None else depth, records, bins.tile_ranges, bins.order,
+                          bins.sorted_ids, *cam, T, settings=1 << 13, eps=depth_eps)
+        ops.paint_blend(acc, texture, T, transform)
+        return texture
+
+    @staticmethod
+    def _edit_pair(e):
+        return (e.view, e.canvas) if hasattr(e, "canvas") else (e[0], e[1])
+
+    @torch.no_grad()
+    def edit_texture(self, edits) -> torch.Tensor:
+        """update_edit_texture (gstex.py:427-437): a fresh SH2RGB(texture_dc[:n_texels]) with every edit of the list
+        -- gstex_amd.edit.Edit entries or (view, canvas) pairs -- painted on it in order; the tensor to hand to
+        eval_render(view, edit_texture=...).  Undo (handle_undo) is the replay of edits[:-1]."""
+        self.wait_texture()
+        texture = SH2RGB(self.texture_dc.detach()[:self.n_texels])
+        for e in edits:
+            view, canvas = self._edit_pair(e)
+            self.paint(view.to(self.device), canvas.to(self.device), texture)
+        return texture
+
+    @torch.no_grad()
+    def bake_edits(self, edits) -> None:
+        """The same replay written into the model: each edit is blended directly into texture_dc[:n_texels], the
+        SH-DC store (the blend reads SH2RGB of a texel and writes RGB2SH of the result, ops.paint_blend's transform),
+        so texels no stroke reaches keep their bits -- which a SH2RGB -> RGB2SH round trip of the whole store would
+        not.  The Adam moments of texture_dc are left alone (a painted texel's next update still carries its old
+        momentum), as are every other parameter, the gradients and the step counter."""
+        self.wait_texture()
+        store = self.texture_dc.detach()
+        for e in edits:
+            view, canvas = self._edit_pair(e)
+            self._paint(view.to(self.device), canvas.to(self.device), store, (SH_C0, 0.5), 1e-2, None)
 
     def loss(self, rgb: torch.Tensor, gt: torch.Tensor, ssim_lambda: float = 0.2) -> torch.Tensor:
         l1 = torch.abs(gt - rgb).mean()

@@ -8,6 +8,7 @@ path: inputs must be HIP tensors, and a missing library raises (see gstex_amd/_l
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import time
 from typing import NamedTuple, Tuple
@@ -900,3 +901,163 @@ def texture_edit(texture_info, texture_dims, edit_rgb, edit_alpha, depth_lower, 
     _launch("gstex_texture_edit", cam, int(settings), ptr(records), ptr(tile_ranges), ptr(order), ptr(sorted_ids),
             ptr(rgb), ptr(a), ptr(dlo), ptr(dhi), n_texels, ptr(out), st)
     return out
+
+
+# ----------------------------------------------------------------------------------------
+# paint: a stroke scattered into a texel accumulator, then blended into the texels
+# ----------------------------------------------------------------------------------------
+@torch.no_grad()
+def paint_scatter(acc, stroke, depth, records, tile_ranges, tile_order, sorted_ids, viewmat, c2w, fx, fy, cx, cy, H, W,
+                  n_texels, settings=_lib.SETTING_EDIT, eps=1e-2):
+    """gstex_paint_scatter: texture_edit's sums  b * w * (a*rgb, a, 1)  of an (H, W, 4) RGBA stroke (float32 in
+    [0, 1] or uint8, read as v / 255) added into `acc`, an (n_texels, 5) float32 accumulator the caller guarantees is
+    all zero, for the pairs whose hit depth lies in [depth - eps, depth + eps] (depth (H, W): the render of the same
+    records).  records / tile_ranges / tile_order / sorted_ids: the depth render's (records may carry the near-edge-on
+    marks); tile_order may be None (row-major).  A pixel with stroke alpha exactly 0 adds acc[:, 4] only.  n_texels is
+    the caller's number (no read-back here).  Returns acc."""
+    H, W, n_texels = int(H), int(W), int(n_texels)
+    _check(n_texels >= 0, f"n_texels must be >= 0 (got {n_texels})")
+    _check(float(eps) >= 0.0, f"eps must be >= 0 (got {eps})")
+    acc = _f32(acc, "acc", (n_texels, 5))
+    _dev(stroke, "stroke")
+    _check(stroke.dtype in (torch.float32, torch.uint8), f"stroke must be float32 or uint8 (got {stroke.dtype})")
+    _check(tuple(stroke.shape) == (H, W, 4), f"stroke must have shape ({H}, {W}, 4) (got {tuple(stroke.shape)})")
+    _check(acc.is_contiguous() and acc.data_ptr() == acc.contiguous().data_ptr(), "acc must be contiguous")
+    stroke = stroke.contiguous()
+    depth = _f32(depth, "depth", (H, W))
+    records = _f32(records, "records", (None, REC_FLOATS))
+    tr = _i32(tile_ranges, "tile_ranges", (None, 2))
+    tiles = ((W + BLOCK_WIDTH - 1) // BLOCK_WIDTH) * ((H + BLOCK_WIDTH - 1) // BLOCK_WIDTH)
+    _check(tr.shape[0] == tiles, f"tile_ranges must have {tiles} rows for a {H}x{W} image (got {tr.shape[0]})")
+    order = _i32(tile_order, "tile_order", (tiles,)) if tile_order is not None else None
+    ids = _i32(sorted_ids, "sorted_ids", (None,))
+    for name, t in (("stroke", stroke), ("depth", depth), ("records", records), ("tile_ranges", tr),
+                    ("sorted_ids", ids)):
+        _check(t.device == acc.device, f"{name} must be on acc's device {acc.device} (got {t.device})")
+    vm = _viewmat(viewmat)
+    cw = _c2w(c2w)
+    args = _lib.GstexPaintScatterArgs(
+        cam=_lib.make_camera(vm, cw, fx, fy, cx, cy, H, W, BLOCK_WIDTH), settings=int(settings),
+        stroke_dtype=_lib.GT_U8 if stroke.dtype == torch.uint8 else _lib.GT_F32, eps=float(eps), records=ptr(records),
+        tile_ranges=ptr(tr), tile_order=ptr(order), sorted_ids=ptr(ids), stroke=ptr(stroke), depth=ptr(depth),
+        n_texels=n_texels, acc=ptr(acc))
+    _launch("gstex_paint_scatter", ctypes.byref(args), _stream(acc))
+    return acc
+
+
+@torch.no_grad()
+def paint_blend(acc, texture, n_texels, transform=(1.0, 0.0)):
+    """gstex_paint_blend: the blend of gstex.py:603-605 from paint_scatter's sums, in place into texture[:n_texels]
+    (float32 (T, 3), T >= n_texels) where acc[:, 3] > 0; acc is all zero again afterwards.  transform=(scale, shift):
+    the stored texels are read as fma(texture, scale, shift) and written back as (out - shift) / scale -- (SH_C0, 0.5)
+    edits an SH-DC store directly.  Returns texture."""
+    n_texels = int(n_texels)
+    _check(n_texels >= 0, f"n_texels must be >= 0 (got {n_texels})")
+    scale, shift = float(transform[0]), float(transform[1])
+    _check(scale != 0.0 and math.isfinite(scale) and math.isfinite(shift),
+           f"transform must be a finite (scale != 0, shift) (got {transform})")
+    _dev(acc, "acc")
+    _dev(texture, "texture")
+    _check(acc.dtype == torch.float32 and acc.is_contiguous() and tuple(acc.shape) == (n_texels, 5),
+           f"acc must be a contiguous float32 ({n_texels}, 5) tensor (got {acc.dtype} {tuple(acc.shape)})")
+    _check(texture.dtype == torch.float32 and texture.is_contiguous() and texture.dim() == 2
+           and texture.shape[1] == 3 and texture.shape[0] >= n_texels,
+           f"texture must be a contiguous float32 (>= {n_texels}, 3) tensor (got {texture.dtype} "
+           f"{tuple(texture.shape)})")
+    _check(texture.device == acc.device, f"texture must be on acc's device {acc.device} (got {texture.device})")
+    args = _lib.GstexPaintBlendArgs(n_texels=n_texels, acc=ptr(acc), texture=ptr(texture), scale=scale, shift=shift)
+    _launch("gstex_paint_blend", ctypes.byref(args), _stream(acc))
+    return texture
+
+
+def _fma32(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """fp32 fused multiply-add a * b + c (one rounding) in torch: the product of two fp32 values is exact in fp64;
+    the fp64 sum is rounded to odd (its error term from the two-sum decides the last bit), after which the rounding
+    to fp32 is the correctly rounded result."""
+    p = a.double() * b.double()
+    c = c.double().expand_as(p)
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)
+    even = (s.view(torch.int64) & 1) == 0
+    toward = torch.where(err > 0, torch.full_like(s, float("inf")), torch.full_like(s, float("-inf")))
+    s = torch.where((err != 0) & even, torch.nextafter(s, toward), s)
+    return s.float()
+
+
+@torch.no_grad()
+def paint_blend_eager(acc, texture, transform=(1.0, 0.0)):
+    """paint_blend restated in torch, on any device: returns the blended copy of `texture` (rows past acc's are
+    passed through); neither input is modified.  The same individually rounded fp32 operations as the kernel."""
+    n = acc.shape[0]
+    scale, shift = float(transform[0]), float(transform[1])
+    identity = scale == 1.0 and shift == 0.0
+    f = dict(device=texture.device, dtype=torch.float32)
+    scale_t, shift_t = torch.tensor(scale, **f), torch.tensor(shift, **f)  # divisors as tensors: true divisions
+    eps = torch.tensor(1e-6, **f)
+    a, wt = acc[:, 3:4], acc[:, 4:5]
+    stored = texture[:n]
+    cur = stored if identity else _fma32(stored, scale_t, shift_t)
+    weight = a / (wt + eps)
+    rgb = acc[:, :3] / (a + eps)
+    out = rgb * weight + cur * (1 - weight)
+    if not identity:
+        out = (out - shift_t) / scale_t
+    res = texture.clone()
+    res[:n] = torch.where(a > 0, out, stored)
+    return res
+
+
+@torch.no_grad()
+def depth_render(texture_dims, centers, num_tiles_hit, opacities, means, scales, glob_scale, quats, uv0, umap, vmap,
+                 viewmat, c2w, fx, fy, cx, cy, H, W, settings, binning: Binning, scratch=None, render=True,
+                 hp: bool | None = None):
+    """The splat records of one geometry and (render=True) its depth map: gstex_raster_setup, then the raster forward
+    with geometry outputs and no texels (colours and texels do not enter the depth) on `binning`'s tile lists.
+    -> (records (N, REC_FLOATS), depth (H, W) or None).  The records carry the near-edge-on marks the forward evaluates
+    (hp: default HP_RECORDS); paint_scatter takes them as they are.  scratch: a dict the per-splat buffers (records,
+    the fp64 rows, the zero colours) are kept in between calls on the same number of splats."""
+    means = _f32(means, "means", (None, 3))
+    n = means.shape[0]
+    H, W = int(H), int(W)
+    _check(binning.n == n and binning.H == H and binning.W == W, "binning was computed for other splats / image size")
+    dims = _i32(texture_dims, "texture_dims", (n, 3))
+    centers_c = _f32(centers, "centers", (n, 2))
+    nth = _i32(num_tiles_hit, "num_tiles_hit", (n,))
+    opacities = _f32(opacities, "opacities", (n, 1))
+    scales = _f32(scales, "scales", (n, 3))
+    quats = _f32(quats, "quats", (n, 4))
+    uv0 = _f32(uv0, "uv0", (n, 1, 2))
+    umap = _f32(umap, "umap", (n, 1, 3))
+    vmap = _f32(vmap, "vmap", (n, 1, 3))
+    vm = _viewmat(viewmat)
+    cw = _c2w(c2w)
+    dev = means.device
+    st = _stream(means)
+    cam = _lib.make_camera(vm, cw, fx, fy, cx, cy, H, W, BLOCK_WIDTH)
+    hp = HP_RECORDS if hp is None else bool(hp)
+    scratch = {} if scratch is None else scratch
+    if scratch.get("key") != (n, dev, hp):
+        scratch.clear()
+        scratch.update(key=(n, dev, hp),
+                       records=torch.empty((n, REC_FLOATS), device=dev, dtype=torch.float32),
+                       hp=torch.empty((n, _lib.HP_DOUBLES), device=dev, dtype=torch.float64) if hp else None,
+                       rgbs=torch.zeros((n, 3), device=dev, dtype=torch.float32))
+    records, hp, rgbs = scratch["records"], scratch["hp"], scratch["rgbs"]
+    _launch("gstex_raster_setup", n, ptr(means), ptr(scales), float(glob_scale), ptr(quats), ptr(rgbs),
+            ptr(opacities), ptr(centers_c), ptr(uv0), ptr(umap), ptr(vmap), ptr(dims), ptr(nth), cam, ptr(records),
+            ptr(hp), st)
+    if not render:
+        return records, None
+    f = dict(device=dev, dtype=torch.float32)
+    img, tex, normal = (torch.empty((H, W, 3), **f) for _ in range(3))
+    alpha, depth, reg = (torch.empty((H, W), **f) for _ in range(3))
+    state = torch.empty((H, W, 4), **f)
+    scene = _lib.GstexRasterScene(
+        cam=cam, channels=3, settings=int(settings), background=None, records=ptr(records), hp_records=ptr(hp),
+        tile_ranges=ptr(binning.tile_ranges), sorted_ids=ptr(binning.sorted_ids), texture=None, n_texels=0,
+        tex_scale=1.0, tex_bias=0.0, state=ptr(state), n_isect=binning.sorted_ids.shape[0], aux=None)
+    fwd = _lib.GstexRasterFwdArgs(scene=scene, tile_order=ptr(binning.order), out_img=ptr(img), out_depth=ptr(depth),
+                                  out_reg=ptr(reg), out_alpha=ptr(alpha), out_tex=ptr(tex), out_normal=ptr(normal))
+    _launch("gstex_raster_fwd", ctypes.byref(fwd), st)
+    return records, depth

@@ -48,7 +48,7 @@ extern "C" {
  * split-backward settings bit of ABI 15 are removed (measured slower).
  * The number counts incompatible changes: an addition that leaves every existing symbol's signature and meaning alone
  * keeps it, and is marked "added within ABI 19 (additive)" where it is declared (gstex_loss_target_*,
- * gstex_eval_metrics*). */
+ * gstex_eval_metrics*, gstex_paint_*). */
 #define GSTEX_ABI_VERSION 19
 
 /* Per-record layout of the splat table written by gstex_raster_setup (floats). */
@@ -355,6 +355,55 @@ int gstex_texture_edit(const gstex_camera* cam, int32_t settings, const float* r
                        const int32_t* tile_ranges, const int32_t* tile_order, const int32_t* sorted_ids,
                        const float* edit_rgb, const float* edit_alpha, const float* depth_lo,
                        const float* depth_hi, int64_t n_texels, float* out, void* stream);
+
+/* Paint a stroke into the texels -- added within ABI 19 (additive).  GStexModel.draw_from_view (gstex.py:489-606) after
+ * its depth render, as two calls on a caller-owned accumulator acc[n_texels][5] that is ALL ZERO on entry to the
+ * scatter and all zero again after the blend (allocate and fill it once; a replay of K edits reuses it).
+ *
+ * gstex_paint_scatter: gstex_texture_edit's traversal, accumulators and guards (the same device function), on the
+ * records, tile lists and tile order the depth render was made from.  Differences:
+ *   - the depth window is formed in the kernel from the rendered depth[H][W]: lo = depth - eps, hi = depth + eps, one
+ *     rounded fp32 operation each (the bits of depth_output -+ 1e-2 in torch, gstex.py:568-569);
+ *   - the stroke is one [H][W][4] image, straight alpha in channel 3: fp32 in [0, 1] (GSTEX_GT_F32, 16-byte aligned)
+ *     or uint8 (GSTEX_GT_U8, 4-byte aligned), value = (float)v / 255.0f (a true division, as gstex_loss_target);
+ *   - a pixel whose stroke alpha is exactly 0 adds only the weight channel acc[.][4]: its other four products are +-0
+ *     and would leave the sums as they are;
+ *   - records may carry gstex_raster_setup's near-edge-on marks (hp_records): this traversal reads the opacity's
+ *     magnitude only and evaluates every pair from the fp32 record, so marked and unmarked tables give the same bits.
+ * settings: as gstex_texture_edit (gstex.py:599 passes 1 << 13 alone: no AA blur in the edit traversal, whatever the
+ * depth render used).
+ *
+ * gstex_paint_blend: one thread per texel t in [0, n_texels) on its row (c0, c1, c2, a, wt).  Where a > 0, each line
+ * one rounded fp32 operation (gstex.py:603-605):
+ *     weight = a / (wt + 1e-6f);  rgb_k = c_k / (a + 1e-6f);  out_k = rgb_k * weight + cur_k * (1 - weight)
+ * written in place into texture[t][3]; where a == 0 the reference's expression returns cur and nothing is written.
+ * cur_k = texture[t][k] for (scale, shift) = (1, 0); otherwise cur_k = fma(texture[t][k], scale, shift) (the fused
+ * multiply-add the raster forward applies tex_scale / tex_bias with) and the write is (out_k - shift) / scale: with
+ * (SH_C0, 0.5) the call edits the SH-DC store itself and texels it does not paint keep their bits.  Every row that was
+ * not all zero is stored back as zeros.  n_texels == 0 launches nothing. */
+typedef struct gstex_paint_scatter_args {
+    gstex_camera cam;
+    int32_t settings;          /* GSTEX_SETTING_* bits gstex_texture_edit accepts; anything else is rejected */
+    int32_t stroke_dtype;      /* GSTEX_GT_F32 or GSTEX_GT_U8 */
+    float eps;                 /* half-width of the depth window, >= 0 (the reference: 1e-2) */
+    const float* records;      /* gstex_raster_setup's table */
+    const int32_t* tile_ranges;
+    const int32_t* tile_order; /* nullable = row-major */
+    const int32_t* sorted_ids;
+    const void* stroke;        /* H*W*4 */
+    const float* depth;        /* H*W: the depth render of the same records */
+    int64_t n_texels;
+    float* acc;                /* n_texels*5, zero on entry */
+} gstex_paint_scatter_args;
+int gstex_paint_scatter(const gstex_paint_scatter_args* args, void* stream);
+typedef struct gstex_paint_blend_args {
+    int64_t n_texels;
+    float* acc;                /* n_texels*5: the scatter's sums; zero again on return */
+    float* texture;            /* at least n_texels*3, edited in place */
+    float scale;               /* finite, not 0 */
+    float shift;               /* finite */
+} gstex_paint_blend_args;
+int gstex_paint_blend(const gstex_paint_blend_args* args, void* stream);
 
 /* ---- splat activations (train-step support) ---------------------------- */
 /* Per splat: quats_n = q/|q|; scales = (clamp(exp(s0),1e-9), clamp(exp(s1),1e-9), 1e-5*mean of those);
