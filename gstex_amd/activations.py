@@ -54,7 +54,7 @@ class _Activate(torch.autograd.Function):
     def backward(ctx, g_qn, g_sc, g_op, *_):
         quats, log_scales, op = ctx.saved_tensors
         n = quats.shape[0]
-        nq, ns, no = ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        _, nq, ns, no, _, _ = ctx.needs_input_grad  # (forward's six inputs, as the return below)
         v_q = torch.empty_like(quats) if nq else None
         v_s = torch.empty_like(log_scales) if ns else None
         v_o = torch.empty_like(op) if no else None

@@ -20,19 +20,17 @@ The rechart every 100 steps (gstex.py:890-914) is provided by `recharge()`.
 """
 from __future__ import annotations
 
-import math
 import os
 from dataclasses import dataclass
 
 import torch
-import torch.nn.functional as F
 
 from . import ops
 from .activations import activate, sh_rest
 from .loss import (ImageMetrics, depth_to_normal, gaussian_window, geometry_loss, image_loss, image_loss_eager,
                    image_metrics, image_metrics_eager, photometric_loss, scheduled)
 from .optim import FusedAdam
-from .charts import SH2RGB, build_charts, get_uv_mapping, texture_dims_to_query
+from .charts import RGB2SH, SH2RGB, SH_C0, build_charts, get_uv_mapping, texture_dims_to_query
 from .scene import Scene, View
 
 # gstex-blender-nvs optimizer settings (gstex_configs.py:207-244)
@@ -49,11 +47,15 @@ DEFAULT_SETTINGS = (1 << 9) | (1 << 10)
 BACKGROUNDS = {"white": (1.0, 1.0, 1.0), "black": (0.0, 0.0, 0.0)}  # background_color names (gstex.py:1012-1020)
 # the fixed colour a background="random" model renders on outside training (gstex.py:355-358)
 VIEWER_BACKGROUND = (0.1490, 0.1647, 0.2157)
-SH_C0 = 0.28209479177387814  # SH2RGB(x) = SH_C0 * x + 0.5 (gstex.py:94-99)
 
 
 def _gauss_window(size=11, sigma=1.5, device=None):
     return gaussian_window(size, sigma).to(device)  # the same fp32 weights the fused kernels use
+
+
+def _composite(img, tex, alpha, bg):
+    """The render on the background `bg` (3,): clamp(img + tex[..., :3] + (1 - alpha) * bg) (gstex.py:1204-1205)."""
+    return torch.clamp(img + tex[..., 0:3] + (1 - alpha[..., None]) * bg[None, None, :], 0.0, 1.0)
 
 
 _BANDS: dict = {}
@@ -137,7 +139,7 @@ class GStexTrainer:
         # reference's JaggedTexture (jagged_texture.py:36-64) it is a capacity store: rows [0, n_texels) are the
         # texels of the current charts, the store only grows at a rechart, and the raster takes the whole store
         # (texture_dims never index past n_texels), so its gradient needs no slice-backward copy
-        tex_dc = (scene.texture[:, :3] - 0.5) / 0.28209479177387814
+        tex_dc = RGB2SH(scene.texture[:, :3])
         self.texture_dc = P(tex_dc)
         self.n_texels = int(tex_dc.shape[0])
         self.texture_dims = scene.texture_dims.to(d).contiguous()
@@ -345,8 +347,7 @@ class GStexTrainer:
             uv0, umap, vmap = get_uv_mapping(quats, self.mappings)
             viewdirs = means.detach() - view.c2w[:3, 3]
             viewdirs = viewdirs / viewdirs.norm(dim=-1, keepdim=True)
-        if self.fix_init and self.sh_degree > 0:
-            viewdirs = torch.stack([viewdirs[:, 0], -viewdirs[:, 2], viewdirs[:, 1]], -1)
+        viewdirs = self._sh_viewdirs(viewdirs)
         intr = (view.fx, view.fy, view.cx, view.cy)
         # project_points / get_aabb_2d / get_num_tiles_hit_2d (gstex.py:1077-1080) in one launch; the centre
         # gradient is chained inside the raster backward (fold_aabb below), the depths only order the tile lists
@@ -367,10 +368,7 @@ class GStexTrainer:
         # forward, so that the binning's placement and sort do not queue behind that wait
         pend = self._pending_tex is not None
         late = pend and self._pending_collective
-        if self.texture_grad_route is not None and torch.is_grad_enabled():
-            sink, zero_sink, on_grad = self.texture_grad_route(self._sink_fresh)
-        else:
-            sink, zero_sink, on_grad = self.texture_grad_sink, self._sink_fresh, self.texture_grad_ready
+        sink, zero_sink, on_grad = self._texel_grad_target()
         guard = None
         if self.pairs is not None and torch.is_grad_enabled():
             self._poll_pairs()
@@ -390,9 +388,20 @@ class GStexTrainer:
             self._cur_zeroed = False
         out = dict(img=img, tex=tex, depth=depth, reg=reg, alpha=alpha, normal=normal)
         if composite:
-            out["rgb"] = torch.clamp(img + tex[:, :, 0:3] + (1 - alpha[:, :, None]) * self.background[None, None, :],
-                                     0.0, 1.0)
+            out["rgb"] = _composite(img, tex, alpha, self.background)
         return out
+
+    def _sh_viewdirs(self, viewdirs):
+        """fix_init (gstex.py:209, the DTU configs): the SH basis is evaluated at (x, -z, y) (gstex.py:1104-1108)."""
+        swap = self.fix_init and self.sh_degree > 0
+        return torch.stack([viewdirs[:, 0], -viewdirs[:, 2], viewdirs[:, 1]], -1) if swap else viewdirs
+
+    def _texel_grad_target(self):
+        """(sink, zero_sink, on_grad) of a render: GradSync's route (the flat buffer's slice, or its side buffer once
+        the tail's collective is on the wire) for a render that records a backward, else the trainer's own sink."""
+        if self.texture_grad_route is not None and torch.is_grad_enabled():
+            return self.texture_grad_route(self._sink_fresh)
+        return self.texture_grad_sink, self._sink_fresh, self.texture_grad_ready
 
     def _fused_ok(self, composite: bool, geometry) -> bool:
         """Whether render() takes gstex_amd.fused's path (see its docstring for why each condition is there)."""
@@ -405,12 +414,7 @@ class GStexTrainer:
     def _render_fused(self, view: View, deg: int):
         from . import fused
 
-        # the texel-gradient target as in the per-op render: GradSync's route (the flat buffer's slice, or its side
-        # buffer once the tail's collective is on the wire) or the trainer's own sink
-        if self.texture_grad_route is not None:
-            sink, zero_sink, on_grad = self.texture_grad_route(self._sink_fresh)
-        else:
-            sink, zero_sink, on_grad = self.texture_grad_sink, self._sink_fresh, self.texture_grad_ready
+        sink, zero_sink, on_grad = self._texel_grad_target()  # (as the per-op render)
         # a deferred texel update that first waits for its collective (GradSync) runs right before the raster forward
         late = self._run_pending_texture if self._pending_tex is not None and self._pending_collective else None
         zero_next = None
@@ -422,10 +426,8 @@ class GStexTrainer:
                                              zero_next)
         self._sink_fresh = False
         self._cur_zeroed = False
-        z = ops._zero_scalar(self.device)  # not rendered: read-only zeros without gradient, as the per-op path
-        H, W = int(view.H), int(view.W)
-        return dict(img=img, tex=tex, depth=z.expand(H, W), reg=z.expand(H, W), alpha=alpha,
-                    normal=z.expand(H, W, 3))
+        depth, reg, normal = ops._zero_views(self.device, int(view.H), int(view.W))  # not rendered, as the per-op path
+        return dict(img=img, tex=tex, depth=depth, reg=reg, alpha=alpha, normal=normal)
 
     @torch.no_grad()
     def eval_render(self, view: View, edit_texture: torch.Tensor | None = None):
@@ -438,8 +440,7 @@ class GStexTrainer:
         means = self.means
         quats, scales, opacities, uv0, umap, vmap, viewdirs = activate(
             means, self.quats, self.scales, self.opacities, self.mappings, view.campos)
-        if self.fix_init and self.sh_degree > 0:
-            viewdirs = torch.stack([viewdirs[:, 0], -viewdirs[:, 2], viewdirs[:, 1]], -1)
+        viewdirs = self._sh_viewdirs(viewdirs)
         intr = (view.fx, view.fy, view.cx, view.cy)
         _, depths = ops.project_points(means, view.viewmat, intr)
         centers, extents = ops.get_aabb_2d(means, scales, 1, quats, view.viewmat, intr)
@@ -481,12 +482,11 @@ class GStexTrainer:
             n_edit, n_unit = None, normal * inv[..., None]
         zeros3 = torch.zeros_like(img)  # texture channels 3..5 of every call
         bg = self._eval_background[None, None, :]  # (the trainer's background; the viewer colour under "random")
-        rgb = torch.clamp(img + tex[..., 0:3] + (1 - alpha[..., None]) * bg, 0.0, 1.0)
         edit_tex_img = n_edit[..., :3] if n_edit is not None else zeros3
-        return dict(rgb=rgb, depth=depth, alpha=alpha, normal=normal,
+        return dict(rgb=_composite(img, tex, alpha, self._eval_background), depth=depth, alpha=alpha, normal=normal,
                     test_img=t_out[0] + (1 - t_out[3][..., None]) * bg,
                     uv_im=torch.clamp(zeros3 + (1 - t_out[3][..., None]) * bg, 0.0, 1.0),
-                    edit_img=torch.clamp(img + edit_tex_img + (1 - alpha[..., None]) * bg, 0.0, 1.0),
+                    edit_img=_composite(img, edit_tex_img, alpha, self._eval_background),
                     clean_normal_img=torch.clamp(0.5 * (n_unit + 1) + (1 - alpha[..., None]) * bg, 0.0, 1.0))
 
     @torch.no_grad()
@@ -503,8 +503,7 @@ class GStexTrainer:
         bg = self._eval_background
         if self.fused_loss:
             return image_metrics(r["img"], r["tex"], r["alpha"], bg, image, out=out)
-        rgb = torch.clamp(r["img"] + r["tex"][:, :, 0:3] + (1 - r["alpha"][:, :, None]) * bg[None, None, :], 0.0, 1.0)
-        res = image_metrics_eager(rgb, bg, image)
+        res = image_metrics_eager(_composite(r["img"], r["tex"], r["alpha"], bg), bg, image)
         if out is not None:
             out.copy_(res.metrics)
             res.metrics = out

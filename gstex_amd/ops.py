@@ -8,9 +8,11 @@ path: inputs must be HIP tensors, and a missing library raises (see gstex_amd/_l
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 import os
 import time
+from collections import namedtuple
 from typing import NamedTuple, Tuple
 
 import torch
@@ -83,22 +85,19 @@ def _dev(t: torch.Tensor, name: str) -> None:
     _check(t.is_cuda, f"{name} must be a HIP (cuda) tensor; gstex_amd has no CPU path (got {t.device})")
 
 
-def _f32(t: torch.Tensor, name: str, shape=None) -> torch.Tensor:
+def _tensor(t: torch.Tensor, name: str, shape=None, *, dtype: torch.dtype) -> torch.Tensor:
+    """A HIP tensor of `dtype` and `shape` (None: any extent in that dimension), contiguous."""
     _dev(t, name)
-    _check(t.dtype == torch.float32, f"{name} must be float32 (got {t.dtype})")
-    if shape is not None:
-        _check(t.dim() == len(shape) and all(s is None or s == d for s, d in zip(shape, t.shape)),
-               f"{name} must have shape {tuple('*' if s is None else s for s in shape)} (got {tuple(t.shape)})")
+    if t.dtype != dtype:  # (the messages are built only when raised: these checks run per splat input per render)
+        raise RuntimeError(f"{name} must be {str(dtype)[len('torch.'):]} (got {t.dtype})")
+    if shape is not None and not (t.dim() == len(shape) and all(s is None or s == d for s, d in zip(shape, t.shape))):
+        raise RuntimeError(
+            f"{name} must have shape {tuple('*' if s is None else s for s in shape)} (got {tuple(t.shape)})")
     return t.contiguous()
 
 
-def _i32(t: torch.Tensor, name: str, shape=None) -> torch.Tensor:
-    _dev(t, name)
-    _check(t.dtype == torch.int32, f"{name} must be int32 (got {t.dtype})")
-    if shape is not None:
-        _check(t.dim() == len(shape) and all(s is None or s == d for s, d in zip(shape, t.shape)),
-               f"{name} must have shape {tuple('*' if s is None else s for s in shape)} (got {tuple(t.shape)})")
-    return t.contiguous()
+_f32 = functools.partial(_tensor, dtype=torch.float32)
+_i32 = functools.partial(_tensor, dtype=torch.int32)
 
 
 def _viewmat(viewmat: torch.Tensor) -> torch.Tensor:
@@ -288,14 +287,21 @@ def _read_count(x: torch.Tensor) -> int:
     return _finish_count(_start_count(x))
 
 
+def _scan_offsets(nth: torch.Tensor, guard=None) -> torch.Tensor:
+    """The exclusive scan of num_tiles_hit -> offsets (n+1,); guard: PairCapacity's, told the pair total offsets[n]."""
+    n = nth.shape[0]
+    offsets = torch.empty((n + 1,), device=nth.device, dtype=torch.int32)
+    ws = torch.empty((max(int(_lib.load().gstex_scan_workspace_size(n)), 1),), device=nth.device, dtype=torch.uint8)
+    call("gstex_scan_offsets", n, ptr(nth), ptr(offsets), ptr(ws), ws.numel(),
+         None if guard is None else ctypes.byref(guard), _stream(nth))
+    return offsets
+
+
 def bin_begin(num_tiles_hit):
     """First half of bin_and_sort: the offsets scan and the asynchronous read of the pair count."""
     n = num_tiles_hit.shape[0]
-    dev = num_tiles_hit.device
     nth = _i32(num_tiles_hit, "num_tiles_hit", (n,))
-    offsets = torch.empty((n + 1,), device=dev, dtype=torch.int32)
-    ws = torch.empty((max(int(_lib.load().gstex_scan_workspace_size(n)), 1),), device=dev, dtype=torch.uint8)
-    call("gstex_scan_offsets", n, ptr(nth), ptr(offsets), ptr(ws), ws.numel(), None, _stream(nth))
+    offsets = _scan_offsets(nth)
     pending = _start_count(offsets[n]) if offsets.is_cuda else int(offsets[n].item())
     return nth, offsets, pending
 
@@ -409,12 +415,8 @@ class PairCapacity:
 
     def scan(self, nth: torch.Tensor, step_flag: torch.Tensor, first: bool, tag=None):
         """The offsets scan of one render with the guard: -> (offsets (n+1,), capacity for this render)."""
-        n = nth.shape[0]
         guard, k, cap = self.reserve(step_flag, first, tag, sized=False)
-        offsets = torch.empty((n + 1,), device=nth.device, dtype=torch.int32)
-        ws = torch.empty((max(int(_lib.load().gstex_scan_workspace_size(n)), 1),), device=nth.device, dtype=torch.uint8)
-        call("gstex_scan_offsets", n, ptr(nth), ptr(offsets), ptr(ws), ws.numel(), ctypes.byref(guard), _stream(nth))
-        return offsets, self.commit(k, cap, tag, nth.device)
+        return _scan_offsets(nth, guard), self.commit(k, cap, tag, nth.device)
 
     def reserve(self, step_flag: torch.Tensor, first: bool, tag=None, sized: bool = True):
         """The guard of one render's scan and its ring slot -> (GstexPairGuard, slot, capacity of the render).  The
@@ -475,73 +477,150 @@ def unit_order(unit_cost: torch.Tensor) -> torch.Tensor:
 # ----------------------------------------------------------------------------------------
 # texture_gaussians
 # ----------------------------------------------------------------------------------------
+# the checked per-splat inputs of one raster call (contiguous), its camera and matrices, device and stream
+_Splats = namedtuple("_Splats", "n dev st means dims centers nth opacities scales quats uv0 umap vmap vm cw cam")
+
+
+def _splat_inputs(count: int, texture_dims, centers, num_tiles_hit, opacities, means, scales, quats, uv0, umap, vmap,
+                  viewmat, c2w, fx, fy, cx, cy, H: int, W: int, block_width=BLOCK_WIDTH,
+                  count_msg="texture_info[0] ({count}) != number of splats ({n})") -> _Splats:
+    """The one check of what texture_gaussians, texture_edit and depth_render share.  count: the number of splats the
+    caller's other arguments (texture_info, a Binning) were made for; count_msg is raised when `means` has another."""
+    _check(int(block_width) == BLOCK_WIDTH, f"block_width must be {BLOCK_WIDTH} (got {block_width})")
+    means = _f32(means, "means", (None, 3))
+    n = means.shape[0]
+    if count != n:
+        raise RuntimeError(count_msg.format(count=count, n=n))
+    dims = _i32(texture_dims, "texture_dims", (n, 3))
+    centers = _f32(centers, "centers", (n, 2))
+    nth = _i32(num_tiles_hit, "num_tiles_hit", (n,))
+    opacities = _f32(opacities, "opacities", (n, 1))
+    scales = _f32(scales, "scales", (n, 3))
+    quats = _f32(quats, "quats", (n, 4))
+    uv0 = _f32(uv0, "uv0", (n, 1, 2))
+    umap = _f32(umap, "umap", (n, 1, 3))
+    vmap = _f32(vmap, "vmap", (n, 1, 3))
+    vm = _viewmat(viewmat)
+    cw = _c2w(c2w)
+    cam = _lib.make_camera(vm, cw, fx, fy, cx, cy, H, W, BLOCK_WIDTH)
+    return _Splats(n, means.device, _stream(means), means, dims, centers, nth, opacities, scales, quats, uv0, umap,
+                   vmap, vm, cw, cam)
+
+
+def _raster_setup(s: _Splats, glob_scale, hp: bool, rgbs=None, into=None):
+    """gstex_raster_setup -> (records, the near-edge-on splats' fp64 rows (hp=False: None, NULL to the kernel),
+    colours (rgbs=None: zeros)), allocated here or `into`, that tuple of an earlier call on as many splats."""
+    if into is None:
+        records = torch.empty((s.n, REC_FLOATS), device=s.dev, dtype=torch.float32)
+        rows = torch.empty((s.n, _lib.HP_DOUBLES), device=s.dev, dtype=torch.float64) if hp else None
+        into = (records, rows, torch.zeros((s.n, 3), device=s.dev, dtype=torch.float32) if rgbs is None else rgbs)
+    records, rows, rgbs = into
+    _launch("gstex_raster_setup", s.n, ptr(s.means), ptr(s.scales), float(glob_scale), ptr(s.quats), ptr(rgbs),
+            ptr(s.opacities), ptr(s.centers), ptr(s.uv0), ptr(s.umap), ptr(s.vmap), ptr(s.dims), ptr(s.nth), s.cam,
+            ptr(records), ptr(rows), s.st)
+    return into
+
+
+def _zero_views(device, H: int, W: int):
+    """(depth, reg, normal) of a render that does not produce them: read-only broadcast views of one cached zero (no
+    fill per call; an in-place write into them raises instead of corrupting later calls)."""
+    z = _zero_scalar(device)
+    return z.expand(H, W), z.expand(H, W), z.expand(H, W, 3)
+
+
+def _raster_forward(s: _Splats, H: int, W: int, C: int, settings, records, hp, tile_ranges, sorted_ids, order,
+                    texture=None, background=None, transform=None, geometry=True, needs_bwd=False, zero_buf=None,
+                    texture_ready=None):
+    """The raster forward on one binning's tile lists -> (GstexRasterScene, (img, depth, reg, alpha, tex, normal),
+    state, aux, partials).  needs_bwd: with the forward's record for the backward (`aux`: cull bits, per-unit costs,
+    checkpoints of deep tile lists) and the fast mode's per-splat partial sums (PARTIAL_FLOATS per splat: room for
+    either row width), which the forward's grid zeroes together with zero_buf (no fill passes)."""
+    f = dict(device=s.dev, dtype=torch.float32)
+    img = torch.empty((H, W, 3), **f)
+    alpha = torch.empty((H, W), **f)
+    tex = torch.empty((H, W, C), **f)
+    state = torch.empty((H, W, 4), **f)
+    if geometry:
+        geo = depth, reg, normal = torch.empty((H, W), **f), torch.empty((H, W), **f), torch.empty((H, W, 3), **f)
+    else:
+        depth, reg, normal = _zero_views(s.dev, H, W)
+        geo = (None, None, None)
+    n_isect = sorted_ids.shape[0]
+    nb = int(_lib.load().gstex_raster_aux_bytes(n_isect, tile_ranges.shape[0], C)) if needs_bwd else 0
+    aux = torch.empty((nb,), device=s.dev, dtype=torch.uint8) if needs_bwd else None
+    if callable(texture_ready):  # the caller's texel update, enqueued right before the raster forward
+        texture_ready()
+    elif texture_ready is not None:  # the texels (and the gradient buffer) are updated on another stream
+        torch.cuda.current_stream(s.dev).wait_event(texture_ready)
+    partials = torch.empty((s.n * PARTIAL_FLOATS,), **f) if needs_bwd else None
+    scale, bias = (1.0, 0.0) if transform is None else (float(transform[0]), float(transform[1]))
+    # what the forward and the backward share (the caller keeps the tensors behind the pointers alive)
+    scene = _lib.GstexRasterScene(
+        cam=s.cam, channels=C, settings=int(settings), background=ptr(background), records=ptr(records),
+        hp_records=ptr(hp), tile_ranges=ptr(tile_ranges), sorted_ids=ptr(sorted_ids), texture=ptr(texture),
+        n_texels=0 if texture is None else texture.shape[0], tex_scale=scale, tex_bias=bias, state=ptr(state),
+        n_isect=n_isect, aux=ptr(aux))
+    fwd = _lib.GstexRasterFwdArgs(
+        scene=scene, tile_order=ptr(order), out_img=ptr(img), out_depth=ptr(geo[0]), out_reg=ptr(geo[1]),
+        out_alpha=ptr(alpha), out_tex=ptr(tex), out_normal=ptr(geo[2]),
+        zero_buf=ptr(zero_buf), zero_floats=0 if zero_buf is None else zero_buf.numel(),
+        zero_buf2=ptr(partials), zero_floats2=0 if partials is None else partials.numel())
+    _launch("gstex_raster_fwd", ctypes.byref(fwd), s.st)
+    return scene, (img, depth, reg, alpha, tex, normal), state, aux, partials
+
+
+# what texture_gaussians takes beyond the reference API, as one argument of the autograd node: none of it is an input
+# to autograd (the sink is a gradient target)
+_RasterOptions = namedtuple("_RasterOptions", "texture_transform fold_aabb geometry_outputs grad_enabled binning "
+                            "texture_grad_sink zero_sink on_texture_grad texture_ready before_pair_wait pair_guard")
+
+
 class _TextureGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, texture_info, texture_dims, centers, extents, depths, num_tiles_hit, rgbs, opacities, means,
                 scales, glob_scale, quats, uv0, umap, vmap, texture, viewmat, c2w, fx, fy, cx, cy, H, W,
-                block_width, settings, background, texture_transform=None, fold_aabb=False,
-                geometry_outputs=True, grad_enabled=True, texture_grad_sink=None, on_texture_grad=None,
-                texture_ready=None, binning=None, before_pair_wait=None, zero_sink=False, pair_guard=None):
+                block_width, settings, background, opts):
         N, L, C = (int(v) for v in texture_info)
         _check(L == 1, f"texture_info[1] (texture layers) must be 1 (got {L})")
         _check(1 <= C <= 8, f"texture_info[2] (channels) must be in [1, 8] (got {C})")
-        _check(int(block_width) == BLOCK_WIDTH, f"block_width must be {BLOCK_WIDTH} (got {block_width})")
-        means = _f32(means, "means", (None, 3))
-        n = means.shape[0]
-        _check(N == n, f"texture_info[0] ({N}) != number of splats ({n})")
-        dims = _i32(texture_dims, "texture_dims", (n, 3))
-        centers_c = _f32(centers, "centers", (n, 2))
+        H, W = int(H), int(W)
+        s = _splat_inputs(N, texture_dims, centers, num_tiles_hit, opacities, means, scales, quats, uv0, umap, vmap,
+                          viewmat, c2w, fx, fy, cx, cy, H, W, block_width)
+        n, nth, centers_c, binning = s.n, s.nth, s.centers, opts.binning
         extents_c = _f32(extents.detach(), "extents", (n, 2))
         depths_c = _f32(depths.detach(), "depths", (n,))
-        nth = _i32(num_tiles_hit, "num_tiles_hit", (n,))
         rgbs = _f32(rgbs, "rgbs", (n, 3))
-        opacities = _f32(opacities, "opacities", (n, 1))
-        scales = _f32(scales, "scales", (n, 3))
-        quats = _f32(quats, "quats", (n, 4))
-        uv0 = _f32(uv0, "uv0", (n, 1, 2))
-        umap = _f32(umap, "umap", (n, 1, 3))
-        vmap = _f32(vmap, "vmap", (n, 1, 3))
         texture = _f32(texture, "texture", (None, C))
-        vm = _viewmat(viewmat)
-        cw = _c2w(c2w)
         bg = _f32(background.detach(), "background", (3,)) if background is not None else None
-        H, W = int(H), int(W)
-        dev = means.device
-        st = _stream(means)
-        cam = _lib.make_camera(vm, cw, fx, fy, cx, cy, H, W, BLOCK_WIDTH)
 
         # the pair count is read to the host once; work that does not depend on the tile lists is queued
         # between the copy and the wait, so the device runs it while the host waits and sizes the pair
         # buffers: the splat records and the zeroed texel-gradient buffer of the backward
         capped = None
-        if binning is None and pair_guard is not None:  # capacity mode: no host read of the pair total
-            pcap, step_flag, first, tag = pair_guard
+        if binning is None and opts.pair_guard is not None:  # capacity mode: no host read of the pair total
+            pcap, step_flag, first, tag = opts.pair_guard
             capped = pcap.scan(nth, step_flag, first, tag)
         begun = bin_begin(nth) if binning is None and capped is None else None
-        records = torch.empty((n, REC_FLOATS), device=dev, dtype=torch.float32)
         # backward-only buffers only when a backward can follow: not under torch.no_grad() (eval renders of
         # trainable parameters), where apply() records no graph whatever the inputs' requires_grad
-        needs_bwd = bool(grad_enabled) and any(ctx.needs_input_grad)
-        # the near-edge-on splats' fp64 rows (read by the forward and the backward)
-        hp = torch.empty((n, _lib.HP_DOUBLES), device=dev, dtype=torch.float64) if HP_RECORDS else None
-        _launch("gstex_raster_setup", n, ptr(means), ptr(scales), float(glob_scale), ptr(quats), ptr(rgbs),
-                ptr(opacities), ptr(centers_c), ptr(uv0), ptr(umap), ptr(vmap), ptr(dims), ptr(nth), cam,
-                ptr(records), ptr(hp), st)
+        needs_bwd = bool(opts.grad_enabled) and any(ctx.needs_input_grad)
+        records, hp, _ = _raster_setup(s, glob_scale, HP_RECORDS, rgbs)
         ctx.hp = hp
         ctx.v_texture = None
-        ctx.sink = texture_grad_sink is not None
-        ctx.on_texture_grad = on_texture_grad
-        if needs_bwd and ctx.needs_input_grad[15]:
+        ctx.sink = opts.texture_grad_sink is not None
+        ctx.on_texture_grad = opts.on_texture_grad
+        if needs_bwd and ctx.needs_input_grad[_RASTER_ARGS.index("texture")]:
             if ctx.sink:  # the caller's gradient buffer: zeroed by the raster forward, accumulated into by the
                 # backward, nothing returned to autograd
-                _check(texture_grad_sink.shape == texture.shape and texture_grad_sink.is_contiguous() and
-                       texture_grad_sink.dtype == torch.float32 and texture_grad_sink.device == texture.device,
+                sink = opts.texture_grad_sink
+                _check(sink.shape == texture.shape and sink.is_contiguous() and sink.dtype == torch.float32
+                       and sink.device == texture.device,
                        "texture_grad_sink must be a contiguous fp32 tensor shaped like texture on its device")
-                ctx.v_texture = texture_grad_sink
+                ctx.v_texture = sink
             else:
                 ctx.v_texture = torch.empty_like(texture)  # zeroed by the raster forward (its zero_buf)
-        if before_pair_wait is not None:
-            before_pair_wait()  # caller's work for the device while the host waits for the pair count
+        if opts.before_pair_wait is not None:
+            opts.before_pair_wait()  # caller's work for the device while the host waits for the pair count
         if capped is not None:
             offsets, tile_ranges, sorted_ids, sorted_slots, order = bin_capped(
                 nth, capped[0], capped[1], centers_c.detach(), extents_c, depths_c, H, W, BLOCK_WIDTH)
@@ -554,63 +633,23 @@ class _TextureGaussians(torch.autograd.Function):
             offsets, tile_ranges, sorted_ids, sorted_slots, order = (binning.offsets, binning.tile_ranges,
                                                                      binning.sorted_ids, binning.sorted_slots,
                                                                      binning.order)
-        ctx_scale, ctx_bias = (1.0, 0.0) if texture_transform is None else (float(texture_transform[0]),
-                                                                             float(texture_transform[1]))
-        f = dict(device=dev, dtype=torch.float32)
-        img = torch.empty((H, W, 3), **f)
-        alpha = torch.empty((H, W), **f)
-        tex = torch.empty((H, W, C), **f)
-        state = torch.empty((H, W, 4), **f)
-        if geometry_outputs:
-            depth = torch.empty((H, W), **f)
-            reg = torch.empty((H, W), **f)
-            normal = torch.empty((H, W, 3), **f)
-            geo_ptrs = (ptr(depth), ptr(reg), ptr(normal))
-            if int(settings) & _lib.SETTING_EVAL_NORMAL:
-                ctx.mark_non_differentiable(normal)  # bit 15: unit normals, a forward-only eval output
-        else:  # not produced by the kernel: zeros, no gradient (read-only broadcast views of one cached zero:
-            # no fill per call; an in-place write into them raises instead of corrupting later calls)
-            z = _zero_scalar(f["device"])
-            depth, reg, normal = z.expand(H, W), z.expand(H, W), z.expand(H, W, 3)
-            geo_ptrs = (None, None, None)
-            ctx.mark_non_differentiable(depth, reg, normal)
-        # per (tile, wave, splat) cull bits of the forward for the backward
-        # the forward's record for the backward (cull bits, per-unit costs, checkpoints of deep tile lists)
-        aux = None
-        n_isect = sorted_ids.shape[0]
-        if needs_bwd:
-            nb = int(_lib.load().gstex_raster_aux_bytes(n_isect, tile_ranges.shape[0], C))
-            aux = torch.empty((nb,), device=dev, dtype=torch.uint8)
-        if callable(texture_ready):  # the caller's texel update, enqueued right before the raster forward
-            texture_ready()
-        elif texture_ready is not None:  # the texels (and the gradient buffer) are updated on another stream
-            torch.cuda.current_stream(dev).wait_event(texture_ready)
-        # the buffers the backward accumulates into are zeroed by the forward's grid (no fill passes): the texel
-        # gradient (this call's own buffer, or the caller's sink when zero_sink) and the fast mode's per-splat partial
-        # sums (PARTIAL_FLOATS per splat: room for either row width)
-        zbuf = ctx.v_texture if (not ctx.sink or zero_sink) else None
-        ctx.partials = torch.empty((n * PARTIAL_FLOATS,), device=dev, dtype=torch.float32) if needs_bwd else None
-        # what the forward and the backward share (the tensors behind the pointers are saved below)
-        scene = _lib.GstexRasterScene(
-            cam=cam, channels=C, settings=int(settings), background=ptr(bg), records=ptr(records),
-            hp_records=ptr(hp), tile_ranges=ptr(tile_ranges), sorted_ids=ptr(sorted_ids), texture=ptr(texture),
-            n_texels=texture.shape[0], tex_scale=ctx_scale, tex_bias=ctx_bias, state=ptr(state), n_isect=n_isect,
-            aux=ptr(aux))
-        fwd = _lib.GstexRasterFwdArgs(
-            scene=scene, tile_order=ptr(order), out_img=ptr(img), out_depth=geo_ptrs[0], out_reg=geo_ptrs[1],
-            out_alpha=ptr(alpha), out_tex=ptr(tex), out_normal=geo_ptrs[2],
-            zero_buf=ptr(zbuf), zero_floats=0 if zbuf is None else zbuf.numel(),
-            zero_buf2=ptr(ctx.partials), zero_floats2=0 if ctx.partials is None else ctx.partials.numel())
-        _launch("gstex_raster_fwd", ctypes.byref(fwd), st)
-        ctx.scene = scene
-        ctx.aux = aux
-        ctx.save_for_backward(means, scales, quats, umap, vmap, texture, nth, offsets, tile_ranges, sorted_ids,
-                              sorted_slots, records, state, vm, cw if cw is not None else vm,
-                              bg if bg is not None else vm)
+        # the texel gradient (this call's own buffer, or the caller's sink when zero_sink) is zeroed by the forward
+        zbuf = ctx.v_texture if (not ctx.sink or opts.zero_sink) else None
+        ctx.scene, outputs, state, ctx.aux, ctx.partials = _raster_forward(
+            s, H, W, C, settings, records, hp, tile_ranges, sorted_ids, order, texture, bg, opts.texture_transform,
+            opts.geometry_outputs, needs_bwd, zbuf, opts.texture_ready)
+        if not opts.geometry_outputs:  # depth, reg, normal: zeros, no gradient
+            ctx.mark_non_differentiable(*outputs[1:3], outputs[5])
+        elif int(settings) & _lib.SETTING_EVAL_NORMAL:
+            ctx.mark_non_differentiable(outputs[5])  # bit 15: unit normals, a forward-only eval output
+        # (vm, cw, bg: alive behind the scene's pointers)
+        ctx.save_for_backward(s.means, s.scales, s.quats, s.umap, s.vmap, texture, nth, offsets, tile_ranges,
+                              sorted_ids, sorted_slots, records, state, s.vm, s.cw if s.cw is not None else s.vm,
+                              bg if bg is not None else s.vm)
         ctx.glob_scale = float(glob_scale)
-        ctx.fold_aabb = bool(fold_aabb)
+        ctx.fold_aabb = bool(opts.fold_aabb)
         ctx.set_materialize_grads(False)  # unused outputs' gradients stay None (no zero tensors)
-        return img, depth, reg, alpha, tex, normal
+        return outputs
 
     @staticmethod
     def backward(ctx, v_img, v_depth, v_reg, v_alpha, v_tex, v_normal):
@@ -674,13 +713,19 @@ class _TextureGaussians(torch.autograd.Function):
             v_uv0=ptr(v_uv0))
         _launch("gstex_raster_setup_bwd", ctypes.byref(sb), st)
         v_bg = None
-        if ctx.needs_input_grad[26]:
+        if ctx.needs_input_grad[_RASTER_ARGS.index("background")]:
             v_bg = (v_img * state[..., 0:1]).sum((0, 1)) if v_img is not None else torch.zeros_like(bg)
         if ctx.fold_aabb:
             v_centers = None  # already chained through the AABB centre into v_means / v_scales / v_quats
-        return (None, None, v_centers, None, None, None, v_rgbs, v_opac, v_means, v_scales, None, v_quats, v_uv0,
-                None, None, v_texture, None, None, None, None, None, None, None, None, None, None, v_bg, None, None,
-                None, None, None, None, None, None, None, None, None)
+        grads = [None] * len(_RASTER_ARGS)
+        for name, g in dict(centers=v_centers, rgbs=v_rgbs, opacities=v_opac, means=v_means, scales=v_scales,
+                            quats=v_quats, uv0=v_uv0, texture=v_texture, background=v_bg).items():
+            grads[_RASTER_ARGS.index(name)] = g  # (a name forward does not take raises)
+        return tuple(grads)
+
+
+# forward's argument names, in order: what backward's gradients and needs_input_grad are addressed by
+_RASTER_ARGS = _TextureGaussians.forward.__code__.co_varnames[1:_TextureGaussians.forward.__code__.co_argcount]
 
 
 def texture_gaussians(texture_info, texture_dims, centers, extents, depths, num_tiles_hit, rgbs, opacities, means,
@@ -737,12 +782,13 @@ def texture_gaussians(texture_info, texture_dims, centers, extents, depths, num_
         raise NotImplementedError(
             "texture_gaussians(use_torch_impl=True): gstex_amd ships no CPU rasterizer; "
             "the CPU restatement in oracle/ is test infrastructure only")
+    opts = _RasterOptions(texture_transform=texture_transform, fold_aabb=fold_aabb, geometry_outputs=geometry_outputs,
+                          grad_enabled=torch.is_grad_enabled(), binning=binning, texture_grad_sink=texture_grad_sink,
+                          zero_sink=zero_texture_grad_sink, on_texture_grad=on_texture_grad,
+                          texture_ready=texture_ready, before_pair_wait=before_pair_wait, pair_guard=pair_guard)
     return _TextureGaussians.apply(texture_info, texture_dims, centers, extents, depths, num_tiles_hit, rgbs,
                                    opacities, means, scales, glob_scale, quats, uv0, umap, vmap, texture, viewmat,
-                                   c2w, fx, fy, cx, cy, H, W, block_width, settings, background, texture_transform,
-                                   fold_aabb, geometry_outputs, torch.is_grad_enabled(), texture_grad_sink,
-                                   on_texture_grad, texture_ready, binning, before_pair_wait, zero_texture_grad_sink,
-                                   pair_guard)
+                                   c2w, fx, fy, cx, cy, H, W, block_width, settings, background, opts)
 
 
 class Binning(NamedTuple):
@@ -862,44 +908,25 @@ def texture_edit(texture_info, texture_dims, edit_rgb, edit_alpha, depth_lower, 
         raise NotImplementedError("texture_edit(use_torch_impl=True): gstex_amd has no CPU rasterizer")
     N, L, K = (int(v) for v in texture_info)
     _check(L == 1 and K == 5, f"texture_info must be (N, 1, 5) for texture_edit (got {tuple(texture_info)})")
-    _check(int(block_width) == BLOCK_WIDTH, f"block_width must be {BLOCK_WIDTH} (got {block_width})")
-    means = _f32(means, "means", (None, 3))
-    n = means.shape[0]
-    _check(N == n, f"texture_info[0] ({N}) != number of splats ({n})")
     H, W = int(H), int(W)
-    dims = _i32(texture_dims, "texture_dims", (n, 3))
-    centers_c = _f32(centers, "centers", (n, 2))
+    s = _splat_inputs(N, texture_dims, centers, num_tiles_hit, opacities, means, scales, quats, uv0, umap, vmap,
+                      viewmat, c2w, fx, fy, cx, cy, H, W, block_width)
+    n, dims = s.n, s.dims
     extents_c = _f32(extents, "extents", (n, 2))
     depths_c = _f32(depths, "depths", (n,))
-    nth = _i32(num_tiles_hit, "num_tiles_hit", (n,))
-    opacities = _f32(opacities, "opacities", (n, 1))
-    scales = _f32(scales, "scales", (n, 3))
-    quats = _f32(quats, "quats", (n, 4))
-    uv0 = _f32(uv0, "uv0", (n, 1, 2))
-    umap = _f32(umap, "umap", (n, 1, 3))
-    vmap = _f32(vmap, "vmap", (n, 1, 3))
     rgb = _f32(edit_rgb, "edit_rgb", (H, W, 3))
     a = _f32(edit_alpha.reshape(H, W), "edit_alpha", (H, W))
     dlo = _f32(depth_lower, "depth_lower", (H, W))
     dhi = _f32(depth_upper, "depth_upper", (H, W))
-    vm = _viewmat(viewmat)
-    cw = _c2w(c2w)
-    dev = means.device
-    st = _stream(means)
-    cam = _lib.make_camera(vm, cw, fx, fy, cx, cy, H, W, BLOCK_WIDTH)
     n_texels = int((dims[:, 0].long() * dims[:, 1].long()).sum()) if n else 0
     if n:
         n_texels = max(n_texels, int((dims[:, 2].long() + dims[:, 0].long() * dims[:, 1].long()).max()))
-    out = torch.zeros((n_texels, 5), device=dev, dtype=torch.float32)
-    offsets, tile_ranges, sorted_ids, _ = bin_and_sort(centers_c, extents_c, depths_c, nth, H, W, BLOCK_WIDTH)
+    out = torch.zeros((n_texels, 5), device=s.dev, dtype=torch.float32)
+    offsets, tile_ranges, sorted_ids, _ = bin_and_sort(s.centers, extents_c, depths_c, s.nth, H, W, BLOCK_WIDTH)
     order = tile_order(tile_ranges)
-    records = torch.empty((n, REC_FLOATS), device=dev, dtype=torch.float32)
-    zeros3 = torch.zeros((n, 3), device=dev, dtype=torch.float32)  # colours do not enter the edit
-    _launch("gstex_raster_setup", n, ptr(means), ptr(scales), float(glob_scale), ptr(quats), ptr(zeros3),
-            ptr(opacities), ptr(centers_c), ptr(uv0), ptr(umap), ptr(vmap), ptr(dims), ptr(nth), cam, ptr(records), None,
-            st)
-    _launch("gstex_texture_edit", cam, int(settings), ptr(records), ptr(tile_ranges), ptr(order), ptr(sorted_ids),
-            ptr(rgb), ptr(a), ptr(dlo), ptr(dhi), n_texels, ptr(out), st)
+    records, _, _ = _raster_setup(s, glob_scale, hp=False)  # zero colours: they do not enter the edit
+    _launch("gstex_texture_edit", s.cam, int(settings), ptr(records), ptr(tile_ranges), ptr(order), ptr(sorted_ids),
+            ptr(rgb), ptr(a), ptr(dlo), ptr(dhi), n_texels, ptr(out), s.st)
     return out
 
 
@@ -1017,47 +1044,20 @@ def depth_render(texture_dims, centers, num_tiles_hit, opacities, means, scales,
     -> (records (N, REC_FLOATS), depth (H, W) or None).  The records carry the near-edge-on marks the forward evaluates
     (hp: default HP_RECORDS); paint_scatter takes them as they are.  scratch: a dict the per-splat buffers (records,
     the fp64 rows, the zero colours) are kept in between calls on the same number of splats."""
-    means = _f32(means, "means", (None, 3))
-    n = means.shape[0]
     H, W = int(H), int(W)
-    _check(binning.n == n and binning.H == H and binning.W == W, "binning was computed for other splats / image size")
-    dims = _i32(texture_dims, "texture_dims", (n, 3))
-    centers_c = _f32(centers, "centers", (n, 2))
-    nth = _i32(num_tiles_hit, "num_tiles_hit", (n,))
-    opacities = _f32(opacities, "opacities", (n, 1))
-    scales = _f32(scales, "scales", (n, 3))
-    quats = _f32(quats, "quats", (n, 4))
-    uv0 = _f32(uv0, "uv0", (n, 1, 2))
-    umap = _f32(umap, "umap", (n, 1, 3))
-    vmap = _f32(vmap, "vmap", (n, 1, 3))
-    vm = _viewmat(viewmat)
-    cw = _c2w(c2w)
-    dev = means.device
-    st = _stream(means)
-    cam = _lib.make_camera(vm, cw, fx, fy, cx, cy, H, W, BLOCK_WIDTH)
+    mismatch = "binning was computed for other splats / image size"
+    _check(binning.H == H and binning.W == W, mismatch)
+    s = _splat_inputs(binning.n, texture_dims, centers, num_tiles_hit, opacities, means, scales, quats, uv0, umap, vmap,
+                      viewmat, c2w, fx, fy, cx, cy, H, W, count_msg=mismatch)
     hp = HP_RECORDS if hp is None else bool(hp)
     scratch = {} if scratch is None else scratch
-    if scratch.get("key") != (n, dev, hp):
+    if scratch.get("key") != (s.n, s.dev, hp):
         scratch.clear()
-        scratch.update(key=(n, dev, hp),
-                       records=torch.empty((n, REC_FLOATS), device=dev, dtype=torch.float32),
-                       hp=torch.empty((n, _lib.HP_DOUBLES), device=dev, dtype=torch.float64) if hp else None,
-                       rgbs=torch.zeros((n, 3), device=dev, dtype=torch.float32))
-    records, hp, rgbs = scratch["records"], scratch["hp"], scratch["rgbs"]
-    _launch("gstex_raster_setup", n, ptr(means), ptr(scales), float(glob_scale), ptr(quats), ptr(rgbs),
-            ptr(opacities), ptr(centers_c), ptr(uv0), ptr(umap), ptr(vmap), ptr(dims), ptr(nth), cam, ptr(records),
-            ptr(hp), st)
+        scratch["key"] = (s.n, s.dev, hp)
+    records, rows, _ = scratch["buffers"] = _raster_setup(s, glob_scale, hp, into=scratch.get("buffers"))
     if not render:
         return records, None
-    f = dict(device=dev, dtype=torch.float32)
-    img, tex, normal = (torch.empty((H, W, 3), **f) for _ in range(3))
-    alpha, depth, reg = (torch.empty((H, W), **f) for _ in range(3))
-    state = torch.empty((H, W, 4), **f)
-    scene = _lib.GstexRasterScene(
-        cam=cam, channels=3, settings=int(settings), background=None, records=ptr(records), hp_records=ptr(hp),
-        tile_ranges=ptr(binning.tile_ranges), sorted_ids=ptr(binning.sorted_ids), texture=None, n_texels=0,
-        tex_scale=1.0, tex_bias=0.0, state=ptr(state), n_isect=binning.sorted_ids.shape[0], aux=None)
-    fwd = _lib.GstexRasterFwdArgs(scene=scene, tile_order=ptr(binning.order), out_img=ptr(img), out_depth=ptr(depth),
-                                  out_reg=ptr(reg), out_alpha=ptr(alpha), out_tex=ptr(tex), out_normal=ptr(normal))
-    _launch("gstex_raster_fwd", ctypes.byref(fwd), st)
+    # the forward with geometry outputs, no texels and no record for a backward
+    depth = _raster_forward(s, H, W, 3, settings, records, rows, binning.tile_ranges, binning.sorted_ids,
+                            binning.order)[1][1]
     return records, depth

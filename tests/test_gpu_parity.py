@@ -673,3 +673,58 @@ def test_geometry_outputs_off_matches(deterministic):
     assert grad_norm_err(res[1][3]["texture"], res[0][3]["texture"]) < 1e-6
     assert float(res[0][4].detach().abs().max()) > 0 and float(res[1][4].abs().max()) == 0.0
     assert float(res[1][5].abs().max()) == 0.0 and float(res[1][6].abs().max()) == 0.0
+
+
+# ---------------------------------------------------------------- the raster callers' input checks
+_BAD_SPLAT_INPUTS = [  # (argument, its replacement from the good one, the RuntimeError's message)
+    ("scales", lambda t: t[:, :2], "scales must have shape (4, 3) (got (4, 2))"),
+    ("quats", lambda t: t[:3], "quats must have shape (4, 4) (got (3, 4))"),
+    ("texture_dims", lambda t: t.long(), "texture_dims must be int32 (got torch.int64)"),
+    ("uv0", lambda t: t[:, 0], "uv0 must have shape (4, 1, 2) (got (4, 2))"),
+    ("num_tiles_hit", lambda t: t.float(), "num_tiles_hit must be int32 (got torch.float32)"),
+    ("viewmat", lambda t: t[:2], "viewmat must be (3,4) or (4,4) (got (2, 4))"),
+    ("c2w", lambda t: t[:3], "c2w must be (4,4) (got (3, 4))"),
+    ("block_width", lambda v: 8, "block_width must be 16 (got 8)"),
+    ("texture_info", lambda v: (5,) + tuple(v[1:]), "texture_info[0] (5) != number of splats (4)"),
+]
+
+
+@pytest.mark.parametrize("caller", ["texture_gaussians", "texture_edit", "depth_render"])
+def test_raster_callers_refuse_the_same_bad_inputs(caller):
+    """texture_gaussians, texture_edit and depth_render refuse a bad per-splat input, camera matrix, block width or
+    splat count with the same RuntimeError: one input wrong at a time, every check ahead of the first launch (the
+    good inputs are never run: the tensors hold no scene)."""
+    from gstex_amd import ops
+
+    n, H, W, T = 4, 32, 32, 300
+    f = lambda *s: torch.rand(s, device=DEV)  # noqa: E731
+    i = lambda *s: torch.ones(s, device=DEV, dtype=torch.int32)  # noqa: E731
+    a = dict(texture_dims=i(n, 3), centers=f(n, 2), extents=f(n, 2), depths=f(n), num_tiles_hit=i(n), rgbs=f(n, 3),
+             opacities=f(n, 1), means=f(n, 3), scales=f(n, 3), glob_scale=1.0, quats=f(n, 4), uv0=f(n, 1, 2),
+             umap=f(n, 1, 3), vmap=f(n, 1, 3), texture=f(T, 3), viewmat=f(4, 4), c2w=f(4, 4), fx=30.0, fy=30.0,
+             cx=16.0, cy=16.0, H=H, W=W, block_width=16, settings=(1 << 9) | (1 << 10), edit_rgb=f(H, W, 3),
+             edit_alpha=f(H, W, 1), depth_lower=f(H, W), depth_upper=f(H, W),
+             binning=ops.Binning(n, H, W, i(n), i(n + 1), i(4, 2), i(8), i(8), i(4)))
+    cam = ["viewmat", "c2w", "fx", "fy", "cx", "cy", "H", "W"]
+    splat = ["opacities", "means", "scales", "glob_scale", "quats", "uv0", "umap", "vmap"]
+    order = {
+        "texture_gaussians": ["texture_info", "texture_dims", "centers", "extents", "depths", "num_tiles_hit", "rgbs"]
+        + splat + ["texture"] + cam + ["block_width", "settings"],
+        "texture_edit": ["texture_info", "texture_dims", "edit_rgb", "edit_alpha", "depth_lower", "depth_upper",
+                         "centers", "extents", "depths", "num_tiles_hit"] + splat + cam + ["block_width", "settings"],
+        "depth_render": ["texture_dims", "centers", "num_tiles_hit"] + splat + cam + ["settings", "binning"],
+    }[caller]
+    a["texture_info"] = (n, 1, 5 if caller == "texture_edit" else 3)
+    tried = 0
+    for name, spoil, message in _BAD_SPLAT_INPUTS:
+        if name not in order:  # depth_render takes neither block_width nor texture_info
+            assert caller == "depth_render" and name in ("block_width", "texture_info")
+            continue
+        bad = dict(a)
+        bad[name] = spoil(a[name])
+        with pytest.raises(RuntimeError) as e:
+            getattr(ops, caller)(*[bad[k] for k in order])
+        assert str(e.value) == message, (caller, name)
+        assert type(e.value) is RuntimeError
+        tried += 1
+    assert tried == (7 if caller == "depth_render" else 9)
