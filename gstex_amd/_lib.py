@@ -148,6 +148,7 @@ ADAM_ZERO_GRAD = 1  # GSTEX_ADAM_ZERO_GRAD
 ADAM_GRID_SHIFT = 8  # GSTEX_ADAM_GRID_SHIFT
 BIN_CAPPED = 1  # GSTEX_BIN_CAPPED
 BIN_COUNT_ZEROED = 2  # GSTEX_BIN_COUNT_ZEROED
+BWD_GENERIC, BWD_TRAIN = 0, 1  # GSTEX_BWD_*: what gstex_raster_bwd_variant returns
 _P = c_void_p
 _CAM = POINTER(GstexCamera)
 
@@ -185,6 +186,7 @@ SIGNATURES = {
     "gstex_unit_order": (c_int32, [c_int32, _P, _P, _P, _P]),
     "gstex_unit_order_scratch_words": (c_size_t, []),
     "gstex_raster_bwd": (c_int32, [POINTER(GstexRasterBwdArgs), _P]),
+    "gstex_raster_bwd_variant": (c_int32, [POINTER(GstexRasterBwdArgs)]),
     "gstex_raster_setup_bwd": (c_int32, [POINTER(GstexRasterSetupBwdArgs), _P]),
     "gstex_sh_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "gstex_sh_bwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P]),

@@ -488,7 +488,9 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(int H, int W, int C, cons
     d_img[3 * pix] = gch[0];
     d_img[3 * pix + 1] = gch[1];
     d_img[3 * pix + 2] = gch[2];
-    for (int c = 0; c < C; ++c) d_tex[(size_t)C * pix + c] = c == 0 ? gch[0] : (c == 1 ? gch[1] : (c == 2 ? gch[2] : 0.0f));
+    // (d_tex NULL: the caller's d_tex is d_img, C = 3, the same image, already written)
+    if (d_tex)
+        for (int c = 0; c < C; ++c) d_tex[(size_t)C * pix + c] = c == 0 ? gch[0] : (c == 1 ? gch[1] : (c == 2 ? gch[2] : 0.0f));
     d_alpha[pix] = -((gch[0] * bg[0] + gch[1] * bg[1]) + gch[2] * bg[2]);
 }
 
@@ -645,8 +647,12 @@ struct FwdOut {
 };
 struct BwdArgs {
     const float* grad_loss;
-    float *d_img, *d_tex, *d_alpha;
+    float *d_img, *d_tex, *d_alpha;  // d_tex NULL: not stored (the caller passed d_tex == d_img)
 };
+// One gradient image for both outputs (d_tex == d_img, C = 3): the kernel writes it once
+BwdArgs bwd_args(const float* grad_loss, float* d_img, float* d_tex, float* d_alpha) {
+    return BwdArgs{grad_loss, d_img, d_tex == d_img ? nullptr : d_tex, d_alpha};
+}
 struct MetricsOut {
     float* rgb_out;
     unsigned char* rgb_u8_out;
@@ -745,9 +751,10 @@ extern "C" int gstex_loss_bwd(int32_t H, int32_t W, int32_t C, const float* img,
                             img && tex && alpha && background && gt && window && grad_loss && d_img && d_tex && d_alpha,
                             workspace, workspace_bytes, gstex_loss_workspace_size(H, W)))
         return rc;
+    GSTEX_REQUIRE(d_tex != d_img || C == 3, "%s: d_tex may be d_img only with C == 3 (got %d)", fn, C);
     const LossLaunch a = loss_launch(H, W, C, img, tex, alpha, background, gt, nullptr, window, ssim_lambda, workspace,
                                      2, stream);
-    launch<GSTEX_GT_F32, 3, kMaskNone>(a, BwdArgs{grad_loss, d_img, d_tex, d_alpha});
+    launch<GSTEX_GT_F32, 3, kMaskNone>(a, bwd_args(grad_loss, d_img, d_tex, d_alpha));
     return launch_status(fn);
 }
 
@@ -781,9 +788,10 @@ extern "C" int gstex_loss_target_bwd(int32_t H, int32_t W, int32_t C, const floa
                             img && tex && alpha && background && window && grad_loss && d_img && d_tex && d_alpha,
                             workspace, workspace_bytes, gstex_loss_target_workspace_size(H, W)))
         return rc;
+    GSTEX_REQUIRE(d_tex != d_img || C == 3, "%s: d_tex may be d_img only with C == 3 (got %d)", fn, C);
     const LossLaunch a = loss_launch(H, W, C, img, tex, alpha, background, target->gt, target->mask, window,
                                      ssim_lambda, workspace, 3, stream);
-    dispatch_target(*target, a, BwdArgs{grad_loss, d_img, d_tex, d_alpha});
+    dispatch_target(*target, a, bwd_args(grad_loss, d_img, d_tex, d_alpha));
     return launch_status(fn);
 }
 

@@ -56,20 +56,28 @@ constexpr int kThreads = kTilePixels;  // 256
 #ifndef GSTEX_XCD_MB
 #define GSTEX_XCD_MB 2  // backward units of one 2x2-tile macro-block dispatched to one XCD (unit_order groups)
 #endif
-// Backward occupancy: waves per SIMD the register allocation targets, per instantiation.  The photometric
-// training variant (C = 3, no geometry gradients) fits 7 (72 VGPRs, no spills; 8 forces 64 VGPRs with scratch
-// spills and is 3 % slower); the others 5.  Measured: warming the next visit's record line with a scalar load
-// during the current visit gains nothing (records hit in cache).
+// Backward occupancy: waves per SIMD the register allocation targets, per instantiation.  The generic photometric
+// build (C = 3, no geometry gradients) fits 7 (72 VGPRs; 1 VGPR + 5 SGPR spills, none in the visit loop; at 8 it
+// takes 7 + 23 and measured 3 % slower); the others 5.  The training call (TRAIN: one upstream gradient for img and
+// tex, no deterministic rows) drops a register set, the slot load and the row branch, which leaves 1 VGPR + 12 SGPR
+// spills at 8 waves (64 VGPRs, 78 SGPRs): the word loop reloads them, the visit loop only in the unstaged-block
+// branch (4 v_readlane, blocks above kTexStage / 3 texels); measured 1347 us against the generic build's 1380 ..
+// 1387 (TRAIN at 7 waves: spill-free, 1368 .. 1372; profiles/bwd_train_summary.md).
+// Measured: warming the next visit's record line with a scalar load during the current visit gains nothing
+// (records hit in cache).
 #ifndef GSTEX_BWD_WAVES_TRAIN
 #define GSTEX_BWD_WAVES_TRAIN 7
 #endif
 #ifndef GSTEX_BWD_WAVES
 #define GSTEX_BWD_WAVES 5
 #endif
-template <int C, bool GEO>
+#ifndef GSTEX_BWD_WAVES_TRAINCALL
+#define GSTEX_BWD_WAVES_TRAINCALL 8
+#endif
+template <int C, bool GEO, bool TRAIN = false>
 struct BwdShape {
     static constexpr bool kTrain = (C == 3 && !GEO);
-    static constexpr int kWaves = kTrain ? GSTEX_BWD_WAVES_TRAIN : GSTEX_BWD_WAVES;
+    static constexpr int kWaves = TRAIN ? GSTEX_BWD_WAVES_TRAINCALL : kTrain ? GSTEX_BWD_WAVES_TRAIN : GSTEX_BWD_WAVES;
 };
 // Backward per-wave texel staging: one splat's texel block (h * w * C int32 fixed-point entries) at a time, 4 KiB
 // per wave (341 texels at C = 3; cfg3's largest block is 169); a larger block adds its run tails straight to global
@@ -990,6 +998,11 @@ __device__ __forceinline__ bool seg_reduce_rows(int key, float (&v)[NV]) {
 // GEO = false: no depth / distortion / normal upstream gradient (all NULL, the training default:
 // gstex.py:198-201 sets both weights to 0), so every term they scale is dropped at compile time.  The
 // remaining arithmetic is unchanged (x + 0 * y = x), so both variants give the same values.
+//
+// TRAIN = true (C = 3, GEO = false; gstex_raster_bwd_variant): the photometric training step's call, whose facts
+// are known before the launch -- v_tex is v_img (the loss's one gradient image for both outputs), v_img and v_alpha
+// are given, and the accumulation is the float-atomic one.  dL/dtex is then dL/dimg's registers, and the emission
+// slot and the row stores are gone; every sum is formed in the generic build's order.
 
 // Texel-gradient fixed point, per visit: the reduce also sums M = sum over the wave's pixels of |w tex_scale| x
 // max_c |dL/dtex[c]|, a bound on what the visit adds to any staged entry (bilinear weights <= 1).  Contributions
@@ -1012,8 +1025,8 @@ constexpr int kFlushU = GSTEX_FLUSH_U;  // staging entries per lane per flush pa
 static_assert(kTexStage % (64 * kFlushU) == 0, "flush passes tile the staging area");
 
 
-template <int C, bool GEO>
-__global__ __launch_bounds__(64, (BwdShape<C, GEO>::kWaves)) void raster_bwd_kernel(
+template <int C, bool GEO, bool TRAIN = false>
+__global__ __launch_bounds__(64, (BwdShape<C, GEO, TRAIN>::kWaves)) void raster_bwd_kernel(
     CamArgs cam_args, int tiles_x, int settings, const float* __restrict__ bg, int Cdyn,
     const float4* __restrict__ records, const double* __restrict__ hp_records, const int2* __restrict__ tile_ranges,
     const int32_t* __restrict__ sorted_ids, const int32_t* __restrict__ sorted_slots, const float* __restrict__ texture,
@@ -1021,6 +1034,7 @@ __global__ __launch_bounds__(64, (BwdShape<C, GEO>::kWaves)) void raster_bwd_ker
     const float* __restrict__ v_depth, const float* __restrict__ v_reg, const float* __restrict__ v_alpha,
     const float* __restrict__ v_tex, const float* __restrict__ v_normal, float* __restrict__ partials,
     unsigned char* __restrict__ row_flags, float* __restrict__ v_texture, const AuxPtrs aux, const ZeroBufs zb) {
+    static_assert(!TRAIN || (C == 3 && !GEO), "the training call is photometric, 3 channels");
     zero_bufs(zb);
     const Camera cam = load_camera(cam_args);
     constexpr int CM = (C > 0) ? C : 8;
@@ -1054,11 +1068,13 @@ __global__ __launch_bounds__(64, (BwdShape<C, GEO>::kWaves)) void raster_bwd_ker
         const float4 st = state[pix];
         T = st.x; M1f = st.y; M2f = st.z; last = __float_as_int(st.w);
         // a NULL upstream gradient (an output the loss does not use) counts as zero
-        if (v_img) { Gimg[0] = v_img[3 * pix]; Gimg[1] = v_img[3 * pix + 1]; Gimg[2] = v_img[3 * pix + 2]; }
+        if (TRAIN || v_img) { Gimg[0] = v_img[3 * pix]; Gimg[1] = v_img[3 * pix + 1]; Gimg[2] = v_img[3 * pix + 2]; }
 #pragma unroll
-        for (int c = 0; c < CM; ++c)
-            if (c < Cn && v_tex) Gtex[c] = v_tex[(size_t)Cn * pix + c];
-        Ga = v_alpha ? v_alpha[pix] : 0.f;
+        for (int c = 0; c < CM; ++c) {
+            if constexpr (TRAIN) Gtex[c] = Gimg[c];  // v_tex is v_img: one set of registers
+            else if (c < Cn && v_tex) Gtex[c] = v_tex[(size_t)Cn * pix + c];
+        }
+        Ga = (TRAIN || v_alpha) ? v_alpha[pix] : 0.f;
         if (GEO) {
             Gd = v_depth ? v_depth[pix] : 0.f;
             Greg = (dreg && v_reg) ? v_reg[pix] : 0.f;
@@ -1121,14 +1137,15 @@ __global__ __launch_bounds__(64, (BwdShape<C, GEO>::kWaves)) void raster_bwd_ker
         int my_gid = 0, my_slot = 0;
         if ((todo >> lane) & 1ull) {
             my_gid = sorted_ids[rng.x + pos0 + lane];
-            my_slot = sorted_slots[rng.x + pos0 + lane];
+            if constexpr (!TRAIN) my_slot = sorted_slots[rng.x + pos0 + lane];  // (the row path's: TRAIN has none)
         }
 #if GSTEX_WORD_WAIT
         // wait for the word's ids here, once: otherwise the waitcnt pass, which merges the loop's entry (ids
         // pending) with its back edge (the previous visit's atomics pending), waits at the top of EVERY visit for
         // all but one of the previous visit's atomics before the record can be addressed (vmcnt counts the
         // no-return atomics in order with the loads)
-        asm volatile("; word ids %0 %1" ::"v"(my_gid), "v"(my_slot));
+        if constexpr (TRAIN) asm volatile("; word ids %0" ::"v"(my_gid));
+        else asm volatile("; word ids %0 %1" ::"v"(my_gid), "v"(my_slot));
 #endif
         while (todo) {
             const int j = 63 - __builtin_clzll(todo);
@@ -1299,7 +1316,7 @@ __global__ __launch_bounds__(64, (BwdShape<C, GEO>::kWaves)) void raster_bwd_ker
                 // accumulator row (zeroed by the caller): no row traffic, no summing pass, order-dependent rounding
                 constexpr int E = NP / 8;
                 const int base = (NP / 2) * ((lane >> 5) & 1) + (NP / 4) * ((lane >> 4) & 1) + E * ((lane >> 3) & 1);
-                if (row_flags) {
+                if (!TRAIN && row_flags) {
                     const int slot = __builtin_amdgcn_readlane(my_slot, j);
                     if ((lane & 7) == 0) {
                         float* dst = partials + ((size_t)slot * 4 + quad) * NP + base;  // rows NP floats apart
@@ -1915,6 +1932,18 @@ extern "C" int gstex_raster_fwd(const gstex_raster_fwd_args* a, void* stream) {
     return launch_status("gstex_raster_fwd");
 }
 
+// depth / distortion / normal gradients present?  (the distortion one only counts when enabled)
+static bool bwd_has_geo(const gstex_raster_bwd_args* a) {
+    return a->v_depth || a->v_normal || (a->v_reg && (a->scene.settings & GSTEX_SETTING_DIST_REG));
+}
+
+extern "C" int gstex_raster_bwd_variant(const gstex_raster_bwd_args* a) {
+    if (!a) return -1;
+    const bool train = a->scene.channels == 3 && !bwd_has_geo(a) && !a->row_flags && a->v_img && a->v_alpha &&
+                       a->v_tex && a->v_tex == a->v_img;
+    return train ? GSTEX_BWD_TRAIN : GSTEX_BWD_GENERIC;
+}
+
 extern "C" int gstex_raster_bwd(const gstex_raster_bwd_args* a, void* stream) {
     GSTEX_REQUIRE(a, "gstex_raster_bwd: null args");
     GSTEX_REQUIRE(a->zero_floats >= 0 && (a->zero_floats == 0 || a->zero_buf) &&
@@ -1949,16 +1978,16 @@ extern "C" int gstex_raster_bwd(const gstex_raster_bwd_args* a, void* stream) {
     // costliest units first, from the histogram the forward built (order entries are unit + 1)
     rc = unit_order_from_hist((int32_t)al.n_units, ap.cost, ap.order, ap.order_ws, st);
     if (rc) return rc;
-    // depth / distortion / normal gradients present?  (the distortion one only counts when enabled)
-    const bool geo = a->v_depth || a->v_normal || (a->v_reg && (settings & GSTEX_SETTING_DIST_REG));
+    const bool geo = bwd_has_geo(a);
     const ZeroBufs zbuf{{a->zero_floats > 0 ? a->zero_buf : nullptr, nullptr}, {a->zero_floats, 0}};
-#define GSTEX_BWD(CC, GG)                                                                                      \
-    raster_bwd_kernel<CC, GG><<<(unsigned)al.n_units, 64, 0, st>>>(                                            \
+#define GSTEX_BWD(CC, ...)                                                                                     \
+    raster_bwd_kernel<CC, __VA_ARGS__><<<(unsigned)al.n_units, 64, 0, st>>>(                                   \
         dc, tiles_x, settings, s.background, channels, (const float4*)s.records, s.hp_records,                \
         (const int2*)s.tile_ranges, s.sorted_ids, a->sorted_slots, s.texture, (int)s.n_texels, s.tex_scale,   \
         s.tex_bias, (const float4*)s.state, a->v_img, a->v_depth, a->v_reg, a->v_alpha, a->v_tex, a->v_normal, \
         a->partials, (unsigned char*)a->row_flags, a->v_texture, ap, zbuf)
-    if (channels == 3 && !geo) GSTEX_BWD(3, false);
+    if (gstex_raster_bwd_variant(a) == GSTEX_BWD_TRAIN) GSTEX_BWD(3, false, /*TRAIN=*/true);
+    else if (channels == 3 && !geo) GSTEX_BWD(3, false);
     else if (channels == 3) GSTEX_BWD(3, true);
     else if (channels == 6 && !geo) GSTEX_BWD(6, false);
     else if (channels == 6) GSTEX_BWD(6, true);

@@ -152,6 +152,7 @@ class _TrainRender(torch.autograd.Function):
         st = _lib.stream_of(dev)
         c = lambda t: None if t is None else t.contiguous()  # noqa: E731
         v_img, v_alpha, v_tex = c(v_img), c(v_alpha), c(v_tex)
+        # (the fused loss delivers ONE tensor as v_img and v_tex: equal addresses select the backward's training build)
         bwd = _lib.GstexRasterBwdArgs(
             scene=scene, sorted_slots=P["sorted_slots"], v_img=ptr(v_img), v_alpha=ptr(v_alpha), v_tex=ptr(v_tex),
             partials=P["partials"], v_texture=ptr(ctx.sink))

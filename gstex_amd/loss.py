@@ -106,7 +106,9 @@ def _backward(ctx, g_loss, n_inputs):
     H, W = alpha.shape
     C = tex.shape[2]
     d_img = torch.empty_like(img)
-    d_tex = torch.empty_like(tex)
+    # at C = 3 both gradients are the same image (d_tex[0..2] = d_img): one tensor, written once, which the raster
+    # backward recognises by its address (gstex_raster_bwd_variant); ctx.share_grad = False keeps two tensors
+    d_tex = d_img if C == 3 and ctx.share_grad else torch.empty_like(tex)
     d_alpha = torch.empty_like(alpha)
     g = g_loss.detach().to(torch.float32).contiguous()
     if ctx.dataset_target:
@@ -121,7 +123,7 @@ def _backward(ctx, g_loss, n_inputs):
 
 class _PhotometricLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, img, tex, alpha, background, gt, ssim_lambda):
+    def forward(ctx, img, tex, alpha, background, gt, ssim_lambda, share_grad=True):
         _check_args("photometric_loss", img, tex, alpha, background, gt, gt=True)
         img, tex, alpha, background, gt, _, ws = _prepare("gstex_loss_workspace_size", img, tex, alpha, background, gt,
                                                           image_align=4)
@@ -133,6 +135,7 @@ class _PhotometricLoss(torch.autograd.Function):
              float(ssim_lambda), ptr(rgb), ptr(out), ptr(ws), ws.numel(), _lib.stream_of(img.device))
         ctx.save_for_backward(img, tex, alpha, background, gt, ws)
         ctx.ssim_lambda = float(ssim_lambda)
+        ctx.share_grad = bool(share_grad)
         ctx.dataset_target = False
         ctx.mark_non_differentiable(rgb)
         ctx.set_materialize_grads(False)  # rgb's (always unused) gradient stays None, no zero image
@@ -140,12 +143,14 @@ class _PhotometricLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, g_rgb):
-        return _backward(ctx, g_loss, 6)
+        return _backward(ctx, g_loss, 7)
 
 
-def photometric_loss(img, tex, alpha, background, gt, ssim_lambda: float = 0.2):
-    """Returns (loss, rgb): loss is the differentiable 0-dim training loss, rgb the composited image."""
-    return _PhotometricLoss.apply(img, tex, alpha, background, gt, ssim_lambda)
+def photometric_loss(img, tex, alpha, background, gt, ssim_lambda: float = 0.2, share_grad: bool = True):
+    """Returns (loss, rgb): loss is the differentiable 0-dim training loss, rgb the composited image.  share_grad: with
+    a 3-channel tex, img and tex receive ONE gradient tensor (the same image; the raster backward then reads it once
+    and takes its training build); False gives each its own."""
+    return _PhotometricLoss.apply(img, tex, alpha, background, gt, ssim_lambda, share_grad)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -186,7 +191,7 @@ def _check_target(name, alpha, image, mask):
 
 class _ImageLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, img, tex, alpha, background, image, mask, ssim_lambda):
+    def forward(ctx, img, tex, alpha, background, image, mask, ssim_lambda, share_grad=True):
         mask = _check_args("image_loss", img, tex, alpha, background, image, mask)
         img, tex, alpha, background, image, mask, ws = _prepare("gstex_loss_target_workspace_size", img, tex, alpha,
                                                                 background, image, mask)
@@ -202,6 +207,7 @@ class _ImageLoss(torch.autograd.Function):
         saved = (img, tex, alpha, background, image, ws) + ((mask,) if mask is not None else ())
         ctx.save_for_backward(*saved)
         ctx.ssim_lambda = float(ssim_lambda)
+        ctx.share_grad = bool(share_grad)
         ctx.dataset_target = True
         ctx.mark_non_differentiable(rgb, gt, terms)
         ctx.set_materialize_grads(False)
@@ -209,16 +215,17 @@ class _ImageLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, g_rgb, g_gt, g_terms):
-        return _backward(ctx, g_loss, 7)
+        return _backward(ctx, g_loss, 8)
 
 
-def image_loss(img, tex, alpha, background, image, mask=None, ssim_lambda: float = 0.2) -> ImageLoss:
+def image_loss(img, tex, alpha, background, image, mask=None, ssim_lambda: float = 0.2,
+               share_grad: bool = True) -> ImageLoss:
     """The training loss of get_loss_dict on the raw rasterizer outputs and the image a dataset delivers, in one
     forward and one backward launch: `image` is float32 or uint8 (v / 255, get_gt_img), (H, W, 3) or (H, W, 4)
     (straight alpha, composited on `background` as composite_with_background does); `mask` is bool or float32,
     (H, W) or (H, W, 1): L1 and SSIM see gt * mask and rgb * mask (gstex.py:1294-1299), the MSE does not.
-    `background` is read on the device by the kernels (no host synchronisation)."""
-    loss, rgb, gt, terms = _ImageLoss.apply(img, tex, alpha, background, image, mask, ssim_lambda)
+    `background` is read on the device by the kernels (no host synchronisation).  share_grad: as photometric_loss."""
+    loss, rgb, gt, terms = _ImageLoss.apply(img, tex, alpha, background, image, mask, ssim_lambda, share_grad)
     return ImageLoss(loss, rgb, gt, terms)
 
 

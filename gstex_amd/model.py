@@ -117,7 +117,8 @@ class GStexTrainer:
                  fused_loss: bool = True, fused_activations: bool = True, geometry_outputs: bool = False,
                  sh_degree_interval: int = 1000, fix_init: bool = False, start_step: int = 0,
                  defer_texture: bool = False, lambda_normal=0.0, lambda_reg=0.0, use_normal_loss: bool = False,
-                 pair_capacity: bool | None = None, fused_step: bool | None = None, background_seed: int = 0):
+                 pair_capacity: bool | None = None, fused_step: bool | None = None, background_seed: int = 0,
+                 shared_grad: bool | None = None):
         self.device = torch.device(device)
         d = self.device
         P = lambda t: torch.nn.Parameter(t.detach().to(d).contiguous())  # noqa: E731
@@ -220,6 +221,12 @@ class GStexTrainer:
         if fused_step is None:
             fused_step = os.environ.get("GSTEX_FUSED_STEP", "1") != "0"
         self.fused_step = bool(fused_step)
+        # shared_grad (not in the reference): the fused loss hands the raster backward ONE upstream gradient for the
+        # colour and the texture image (at 3 channels they are the same image), which selects the backward's training
+        # build (gstex_raster_bwd_variant); GSTEX_SHARED_GRAD=0 keeps two tensors and the generic build
+        if shared_grad is None:
+            shared_grad = os.environ.get("GSTEX_SHARED_GRAD", "1") != "0"
+        self.shared_grad = bool(shared_grad)
         self._tex_grad = None
         self._tex_grad_next = None
         self._cur_zeroed = self._next_zeroed = False
@@ -647,12 +654,14 @@ class GStexTrainer:
         if mask is not None or gt.dtype != torch.float32 or gt.shape[-1] != 3:
             # a dataset target: conversion, alpha composite and mask inside the loss kernels (gstex_amd.loss)
             if self.fused_loss:
-                res = image_loss(out["img"], out["tex"], out["alpha"], self.background, gt, mask)
+                res = image_loss(out["img"], out["tex"], out["alpha"], self.background, gt, mask,
+                                 share_grad=self.shared_grad)
             else:
                 res = image_loss_eager(out["rgb"], self.background, gt, mask)
             loss, rgb, terms = res.loss, res.rgb, res.terms
         elif self.fused_loss:  # composite + clamp + L1/SSIM in one HIP launch pair (gstex_amd.loss)
-            loss, rgb = photometric_loss(out["img"], out["tex"], out["alpha"], self.background, gt.contiguous())
+            loss, rgb = photometric_loss(out["img"], out["tex"], out["alpha"], self.background, gt.contiguous(),
+                                         share_grad=self.shared_grad)
         else:
             rgb = out["rgb"]
             loss = self.loss(rgb, gt)

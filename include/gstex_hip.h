@@ -48,7 +48,7 @@ extern "C" {
  * split-backward settings bit of ABI 15 are removed (measured slower).
  * The number counts incompatible changes: an addition that leaves every existing symbol's signature and meaning alone
  * keeps it, and is marked "added within ABI 19 (additive)" where it is declared (gstex_loss_target_*,
- * gstex_eval_metrics*, gstex_paint_*). */
+ * gstex_eval_metrics*, gstex_paint_*, gstex_raster_bwd_variant). */
 #define GSTEX_ABI_VERSION 19
 
 /* Per-record layout of the splat table written by gstex_raster_setup (floats). */
@@ -295,6 +295,15 @@ typedef struct gstex_raster_bwd_args {
     int64_t zero_floats;
 } gstex_raster_bwd_args;
 int gstex_raster_bwd(const gstex_raster_bwd_args* args, void* stream);
+/* Which kernel build gstex_raster_bwd launches for these arguments -- added within ABI 19 (additive); a host-side
+ * query, nothing is launched or validated.  GSTEX_BWD_TRAIN, the photometric training step's call, exactly when:
+ * scene.channels == 3; no depth / normal / (enabled) distortion gradient; row_flags == NULL; v_img, v_alpha and
+ * v_tex given; and v_tex == v_img, ONE upstream gradient for both outputs (at 3 channels the two layouts are the
+ * same, and the loss's gradient for both is the same image: gstex_loss_bwd with d_tex == d_img).  That build reads
+ * it once, carries no deterministic row path and runs at a higher occupancy; its sums are formed in the generic
+ * build's order.  Every other call: GSTEX_BWD_GENERIC.  NULL args: -1. */
+enum { GSTEX_BWD_GENERIC = 0, GSTEX_BWD_TRAIN = 1 };
+int gstex_raster_bwd_variant(const gstex_raster_bwd_args* args);
 /* Sums each splat's flagged partial rows (slot-major, quadrant-minor order: bitwise reproducible) and chains
  * them to the splat parameters. Outputs are overwritten.  partials is consumed: each splat's sums are written
  * over its first row (the rows are backward scratch, not read again). */
@@ -434,7 +443,9 @@ int gstex_sh_rest_bwd(int32_t n, int32_t degree, int32_t n_rest, const float* vi
  * device fp32; tex has C >= 3 channels (only 0..2 enter the loss).  loss_out (device float[3]) =
  * {loss, L1, SSIM}; rgb_out may be NULL.  The forward leaves in the workspace what the backward reads:
  * pass the same workspace to gstex_loss_bwd.  grad_loss is a device scalar (the loss's upstream
- * gradient); d_img, d_tex (channels >= 3 zero) and d_alpha are overwritten. */
+ * gradient); d_img, d_tex (channels >= 3 zero) and d_alpha are overwritten.  With C == 3, d_tex may be d_img (the
+ * same address: the two gradients are the same image, written once; gstex_loss_target_bwd alike); with C > 3 that
+ * is refused. */
 size_t gstex_loss_workspace_size(int32_t H, int32_t W);
 int gstex_loss_fwd(int32_t H, int32_t W, int32_t C, const float* img, const float* tex, const float* alpha,
                    const float* background, const float* gt, const float* window, float ssim_lambda,
