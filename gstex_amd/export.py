@@ -5,7 +5,8 @@ xyz, features_rest, opacity, scaling, rotation, texture_dc, texture_dims, mappin
 their stored, pre-activation form; texture_dc holds SH-DC values, gstex.py:1119).  ``trainer_from_npz``
 rebuilds a ``GStexTrainer`` from such a file bit-exactly (features_dc, which the exporter omits, is zero:
 under SH colour the DC term is replaced by the texture, gstex.py:1100).  ``average_colors`` is
-``GStexModel.get_average_colors`` (gstex.py:714-726), used by the reference's PLY export.
+``GStexModel.get_average_colors`` (gstex.py:714-726), used by the reference's PLY export, which ``export_ply``
+restates (``ExportGStexPly``, exporter.py:52-76) on gstex_amd.ply's writer.
 """
 from __future__ import annotations
 
@@ -52,6 +53,23 @@ def average_colors(texture_dc: torch.Tensor, texture_dims: torch.Tensor, sh_degr
     tex = SH2RGB(tex) if sh_degree > 0 else torch.sigmoid(tex)
     avg = torch.zeros((n, tex.shape[-1]), device=tex.device, dtype=torch.float32)
     return torch.index_add(avg, 0, ids, tex) / hws.float()[:, None]
+
+
+def export_ply(trainer, path) -> None:
+    """ExportGStexPly (scripts/exporter.py:52-76): a point cloud of the splat centres coloured by each splat's mean
+    texel colour, clamp(average_colors, 0, 1).  Little-endian binary, `double x y z` then `uchar red green blue`
+    (the colour times 255, rounded to nearest).  The reference writes the file with open3d's write_point_cloud;
+    these column types and the rounding follow that writer from memory, which cannot be checked here (open3d is
+    absent).  What is checked: the file is a valid `init_lod_ply` (gstex_amd.init.scene_from_point_cloud), the
+    format the reference's own LOD inits use."""
+    from .ply import write_ply
+
+    with torch.no_grad():
+        xyz = trainer.means.detach().cpu().numpy().astype(np.float64)
+        colors = torch.clamp(average_colors(trainer.texels(), trainer.texture_dims, trainer.sh_degree), 0.0, 1.0)
+        rgb = torch.round(colors * 255.0).to(torch.uint8).cpu().numpy()
+    write_ply(path, {"x": xyz[:, 0], "y": xyz[:, 1], "z": xyz[:, 2],
+                     "red": rgb[:, 0], "green": rgb[:, 1], "blue": rgb[:, 2]}, binary=True)
 
 
 def trainer_from_npz(path, device, **trainer_kwargs):

@@ -118,7 +118,7 @@ class GStexTrainer:
                  sh_degree_interval: int = 1000, fix_init: bool = False, start_step: int = 0,
                  defer_texture: bool = False, lambda_normal=0.0, lambda_reg=0.0, use_normal_loss: bool = False,
                  pair_capacity: bool | None = None, fused_step: bool | None = None, background_seed: int = 0,
-                 shared_grad: bool | None = None):
+                 shared_grad: bool | None = None, lrs: dict | None = None):
         self.device = torch.device(device)
         d = self.device
         P = lambda t: torch.nn.Parameter(t.detach().to(d).contiguous())  # noqa: E731
@@ -147,6 +147,10 @@ class GStexTrainer:
         self.mappings = scene.mappings.to(d).contiguous()
         self.sh_degree = sh_degree
         self.settings = settings
+        # lrs: the per-group learning rates of a preset (gstex_amd.train.PRESETS); default LRS (gstex-blender-nvs)
+        self.lrs = dict(LRS if lrs is None else lrs)
+        if set(self.lrs) != set(LRS):
+            raise ValueError(f"lrs must have exactly the groups {sorted(LRS)} (got {sorted(self.lrs)})")
         self.pixel_num = pixel_num if pixel_num is not None else float(scene.texture.shape[0])
         # background: a colour, "white", "black", or "random" (gstex.py:178, 1012-1020): a fresh uniform colour per
         # training step, drawn on the device into this same tensor (refresh_background), which feeds the render's
@@ -322,7 +326,7 @@ class GStexTrainer:
         return [p for ps in self.param_groups().values() for p in ps]
 
     def _build_optimizer(self):
-        groups = [{"params": ps, "lr": LRS[name], "name": name} for name, ps in self.param_groups().items()]
+        groups = [{"params": ps, "lr": self.lrs[name], "name": name} for name, ps in self.param_groups().items()]
         if self.fused_adam:
             self.optimizer = FusedAdam(groups, eps=1e-15)
         else:
