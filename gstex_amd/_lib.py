@@ -123,6 +123,15 @@ class GstexRasterSetupBwdArgs(ctypes.Structure):
             "v_means", "v_scales", "v_quats", "v_rgbs", "v_opacities", "v_centers", "v_uv0")]
 
 
+class GstexRasterViewmatBwdArgs(ctypes.Structure):
+    """gstex_raster_viewmat_bwd_args (added within ABI 19): the raster's view-matrix gradient."""
+    _fields_ = [("n", c_int32), ("glob_scale", c_float), ("row_floats", c_int32), ("fold_aabb", c_int32),
+                ("n_rows", c_int64), ("cam", GstexCamera)] + [
+        (name, c_void_p) for name in (
+            "means", "scales", "quats", "num_tiles_hit", "offsets", "partials", "row_flags", "v_centers", "workspace",
+            "v_viewmat")]
+
+
 class GstexLossTarget(ctypes.Structure):
     """gstex_loss_target (added within ABI 19): the dataset image and mask of gstex_loss_target_fwd / _bwd."""
     _fields_ = [("gt", c_void_p), ("mask", c_void_p), ("gt_dtype", c_int32), ("gt_channels", c_int32),
@@ -188,6 +197,9 @@ SIGNATURES = {
     "gstex_raster_bwd": (c_int32, [POINTER(GstexRasterBwdArgs), _P]),
     "gstex_raster_bwd_variant": (c_int32, [POINTER(GstexRasterBwdArgs)]),
     "gstex_raster_setup_bwd": (c_int32, [POINTER(GstexRasterSetupBwdArgs), _P]),
+    "gstex_raster_viewmat_bwd_workspace": (c_size_t, [c_int32]),
+    "gstex_raster_viewmat_bwd": (c_int32, [POINTER(GstexRasterViewmatBwdArgs), _P]),
+    "gstex_sh_dirs_bwd": (c_int32, [c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P]),
     "gstex_sh_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "gstex_sh_bwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "gstex_texture_sample": (c_int32, [c_int64, c_int32, _P, _P, c_int64, _P, _P, _P]),

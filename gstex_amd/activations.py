@@ -79,17 +79,28 @@ class _SHRest(torch.autograd.Function):
         r = rest.detach().contiguous()
         out = torch.empty((n, 3), device=vd.device, dtype=torch.float32)
         call("gstex_sh_rest_fwd", n, int(degree), r.shape[1], ptr(vd), ptr(r), ptr(out), _lib.stream_of(vd.device))
-        ctx.save_for_backward(vd)
+        if ctx.needs_input_grad[1]:  # camera pose refinement: the direction gradient reads the coefficients
+            ctx.save_for_backward(vd, r)
+        else:
+            ctx.save_for_backward(vd)
         ctx.degree, ctx.K = int(degree), r.shape[1]
         return out
 
     @staticmethod
     def backward(ctx, g):
-        (vd,) = ctx.saved_tensors
+        vd = ctx.saved_tensors[0]
         n = vd.shape[0]
-        v = torch.empty((n, ctx.K, 3), device=vd.device, dtype=torch.float32)
-        call("gstex_sh_rest_bwd", n, ctx.degree, ctx.K, ptr(vd), ptr(g.contiguous()), ptr(v), _lib.stream_of(vd.device))
-        return None, None, v
+        g = g.contiguous()
+        v = None
+        if ctx.needs_input_grad[2]:
+            v = torch.empty((n, ctx.K, 3), device=vd.device, dtype=torch.float32)
+            call("gstex_sh_rest_bwd", n, ctx.degree, ctx.K, ptr(vd), ptr(g), ptr(v), _lib.stream_of(vd.device))
+        v_dirs = None
+        if ctx.needs_input_grad[1] and ctx.K > 0:
+            from .ops import sh_dirs_bwd
+
+            v_dirs = sh_dirs_bwd(ctx.degree, 1, vd, ctx.saved_tensors[1], g)
+        return None, v_dirs, v
 
 
 def sh_rest(degree: int, viewdirs, features_rest):

@@ -345,11 +345,16 @@ class GStexTrainer:
             # launches, instead of idling through them after a synchronisation (the bench's first timed step); it only
             # has to land before the raster forward, the first reader of the texels
             self._run_pending_texture()
-        if self._fused_ok(composite, geometry):
+        if self._fused_ok(composite, geometry, view):
             return self._render_fused(view, deg)
         if self.fused_activations:  # one HIP launch each way (gstex_amd.activations)
             quats, scales, opacities, uv0, umap, vmap, viewdirs = activate(
                 means, self.quats, self.scales, self.opacities, self.mappings, view.campos)
+            if view.c2w.requires_grad and torch.is_grad_enabled():
+                # camera pose refinement (gstex_amd.pose): the kernel's view directions carry no gradient; the torch
+                # expression of the branch below does, to the camera position c2w[:3, 3]
+                viewdirs = means.detach() - view.c2w[:3, 3]
+                viewdirs = viewdirs / viewdirs.norm(dim=-1, keepdim=True)
         else:
             quats = self.quats / self.quats.norm(dim=-1, keepdim=True)
             s = torch.exp(self.scales[:, :-1]).clamp(min=1e-9)
@@ -414,8 +419,11 @@ class GStexTrainer:
             return self.texture_grad_route(self._sink_fresh)
         return self.texture_grad_sink, self._sink_fresh, self.texture_grad_ready
 
-    def _fused_ok(self, composite: bool, geometry) -> bool:
-        """Whether render() takes gstex_amd.fused's path (see its docstring for why each condition is there)."""
+    def _fused_ok(self, composite: bool, geometry, view: View | None = None) -> bool:
+        """Whether render() takes gstex_amd.fused's path (see its docstring for why each condition is there).  A view
+        whose viewmat / c2w require a gradient (camera pose refinement) declines it: that path has no pose chain."""
+        if view is not None and (view.viewmat.requires_grad or view.c2w.requires_grad):
+            return False
         return (self.fused_step and not composite and not (self.geometry_outputs if geometry is None else geometry)
                 and self.fused_activations and self.sh_degree > 0 and not self.fix_init
                 and self.pairs is not None and self.pairs.capacity > 0 and self.texture_grad_sink is not None
@@ -645,10 +653,15 @@ class GStexTrainer:
             self.background.uniform_(0.0, 1.0, generator=self._background_gen)
         return self.background
 
-    def forward_backward(self, view: View, gt: torch.Tensor, mask: torch.Tensor | None = None) -> StepOutput:
+    def forward_backward(self, view: View, gt: torch.Tensor, mask: torch.Tensor | None = None,
+                         extra_loss: torch.Tensor | None = None) -> StepOutput:
         """One training step's loss and gradients.  gt: the target as the dataset delivers it -- float32 or uint8,
         (H, W, 3), or (H, W, 4) with straight alpha (composited on the step's background); mask: bool or float32,
-        (H, W) or (H, W, 1), applied to both images before L1 and SSIM (gstex.py:1294-1299)."""
+        (H, W) or (H, W, 1), applied to both images before L1 and SSIM (gstex.py:1294-1299).
+
+        view: its viewmat / c2w may require a gradient (gstex_amd.pose.PoseRefiner.view): the per-op path then also
+        produces the pose gradient (the fused step declines such a view).  extra_loss: a scalar added to the loss
+        before the backward (the pose regulariser)."""
         lam_n, lam_r = scheduled(self.lambda_normal, self.step), scheduled(self.lambda_reg, self.step)
         geo = lam_n != 0.0 or lam_r != 0.0
         self.refresh_background()
@@ -674,6 +687,8 @@ class GStexTrainer:
             est = (depth_to_normal(out["depth"], view.viewmat, view.c2w, view.fx, view.fy, view.cx, view.cy).detach()
                    if self.use_normal_loss else out["normal"])
             loss = loss + geometry_loss(out["alpha"], out["normal"], est, out["reg"], lam_n, lam_r)
+        if extra_loss is not None:
+            loss = loss + extra_loss
         loss.backward(self._one)  # (a cached seed: no per-step fill launch for the implicit ones_like)
         return StepOutput(loss.detach(), rgb.detach(), terms)
 

@@ -122,6 +122,31 @@ def _stream(t: torch.Tensor) -> int:
     return _lib.stream_of(t.device)
 
 
+def _viewmat_grad_like(g34: torch.Tensor, shape) -> torch.Tensor:
+    """The (3, 4) view-matrix gradient in the shape the caller's viewmat has ((3,4), (4,4) or either with a leading
+    1): the last row of a 4x4 is not read, so its gradient is zero."""
+    if shape[-2] == 4:
+        g34 = torch.cat([g34, g34.new_zeros((1, 4))], 0)
+    return g34.reshape(shape)
+
+
+def _viewmat_bwd(n, glob_scale, cam, means, scales, quats, *, row_floats=0, fold_aabb=False, n_rows=-1, nth=None,
+                 offsets=None, partials=None, row_flags=None, v_centers=None) -> torch.Tensor:
+    """gstex_raster_viewmat_bwd -> dL/d(viewmat) (3, 4): the raster's (partials: after gstex_raster_setup_bwd, on its
+    buffers) or, with v_centers alone, get_aabb_2d's."""
+    dev = means.device
+    ws = torch.empty((max(int(_lib.load().gstex_raster_viewmat_bwd_workspace(n)) // 8, 1),), device=dev,
+                     dtype=torch.float64)
+    v_viewmat = torch.empty((3, 4), device=dev, dtype=torch.float32)
+    args = _lib.GstexRasterViewmatBwdArgs(
+        n=n, glob_scale=float(glob_scale), row_floats=int(row_floats), fold_aabb=int(bool(fold_aabb)),
+        n_rows=int(n_rows), cam=cam, means=ptr(means), scales=ptr(scales), quats=ptr(quats), num_tiles_hit=ptr(nth),
+        offsets=ptr(offsets), partials=ptr(partials), row_flags=ptr(row_flags), v_centers=ptr(v_centers),
+        workspace=ptr(ws), v_viewmat=ptr(v_viewmat))
+    _launch("gstex_raster_viewmat_bwd", ctypes.byref(args), _stream(means))
+    return v_viewmat
+
+
 # ----------------------------------------------------------------------------------------
 # project_points / get_aabb_2d / get_num_tiles_hit_2d
 # ----------------------------------------------------------------------------------------
@@ -137,6 +162,7 @@ class _ProjectPoints(torch.autograd.Function):
         call("gstex_project_points", n, ptr(means), cam, ptr(xys), ptr(depths), _stream(means))
         ctx.save_for_backward(means, vm)
         ctx.intr = (fx, fy, cx, cy)
+        ctx.vm_shape = tuple(viewmat.shape)
         ctx.set_materialize_grads(False)  # the kernel reads a NULL v_xys / v_depths as zero
         return xys, depths
 
@@ -154,7 +180,23 @@ class _ProjectPoints(torch.autograd.Function):
         v_depths = v_depths.contiguous() if v_depths is not None else None
         call("gstex_project_points_bwd", n, ptr(means), cam, ptr(v_xys), ptr(v_depths), ptr(v_means),
              _stream(means))
-        return v_means, None, None, None, None, None
+        v_vm = None
+        if ctx.needs_input_grad[1]:
+            # the view-matrix gradient of the pinhole projection, chained in torch (n x 3 work; no caller has this on
+            # its hot path): p = R mu + t, xy = f p.xy / p.z + c where p.z > clip (else 0), depth = p.z
+            fx, fy, _, _ = ctx.intr
+            p = means.double() @ vm[:, :3].double().T + vm[:, 3].double()
+            ok = p[:, 2] > 0.01  # gstex_common.h kProjClip
+            z = torch.where(ok, p[:, 2], torch.ones_like(p[:, 2]))
+            gx = (v_xys[:, 0].double() * fx / z) * ok if v_xys is not None else torch.zeros_like(z)
+            gy = (v_xys[:, 1].double() * fy / z) * ok if v_xys is not None else torch.zeros_like(z)
+            gz = -(gx * p[:, 0] + gy * p[:, 1]) / z
+            if v_depths is not None:
+                gz = gz + v_depths.double()
+            v_p = torch.stack([gx, gy, gz], -1)
+            v_vm = _viewmat_grad_like(torch.cat([v_p.T @ means.double(), v_p.sum(0)[:, None]], 1).float(),
+                                      ctx.vm_shape)
+        return v_means, v_vm, None, None, None, None
 
 
 def project_points(means: torch.Tensor, viewmat: torch.Tensor, intrinsics) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -178,6 +220,7 @@ class _Aabb2d(torch.autograd.Function):
              ptr(extents), _stream(means))
         ctx.save_for_backward(means, scales, quats, vm)
         ctx.args = (float(glob_scale), fx, fy, cx, cy)
+        ctx.vm_shape = tuple(viewmat.shape)
         ctx.mark_non_differentiable(extents)
         ctx.set_materialize_grads(False)
         return centers, extents
@@ -193,9 +236,14 @@ class _Aabb2d(torch.autograd.Function):
         v_scales = torch.empty_like(scales)
         v_quats = torch.empty_like(quats)
         cam = _lib.make_camera(vm, None, fx, fy, cx, cy, 0, 0, BLOCK_WIDTH)
+        v_centers = v_centers.contiguous()
         call("gstex_aabb_2d_bwd", n, ptr(means), ptr(scales), glob, ptr(quats), cam,
-             ptr(v_centers.contiguous()), ptr(v_means), ptr(v_scales), ptr(v_quats), _stream(means))
-        return v_means, v_scales, None, v_quats, None, None, None, None, None
+             ptr(v_centers), ptr(v_means), ptr(v_scales), ptr(v_quats), _stream(means))
+        v_vm = None
+        if ctx.needs_input_grad[4]:  # camera pose refinement: the centre-only mode of the raster's viewmat gradient
+            v_vm = _viewmat_grad_like(_viewmat_bwd(n, glob, cam, means, scales, quats, v_centers=v_centers),
+                                      ctx.vm_shape)
+        return v_means, v_scales, None, v_quats, v_vm, None, None, None, None
 
 
 def get_aabb_2d(means, scales, glob_scale, quats, viewmat, intrinsics):
@@ -220,7 +268,9 @@ def preprocess(means, scales, glob_scale, quats, viewmat, intrinsics, H: int, W:
     """project_points' depths, get_aabb_2d and get_num_tiles_hit_2d in one launch (gstex_preprocess) ->
     (depths (N,), centers (N,2), extents (N,2), num_tiles_hit (N,) int32), bit-identical to the three calls and
     without autograd: for texture_gaussians(..., fold_aabb=True), whose backward chains the centre gradient itself
-    (the training path; gstex.py:1077-1080)."""
+    (the training path; gstex.py:1077-1080).  No gradient can arrive here, so none is dropped when viewmat requires one
+    (camera pose refinement): the folded raster backward carries the centres' part to viewmat too, and the depths only
+    order the tile lists."""
     fx, fy, cx, cy = [float(v) for v in intrinsics]
     means = _f32(means.detach(), "means", (None, 3))
     n = means.shape[0]
@@ -648,6 +698,7 @@ class _TextureGaussians(torch.autograd.Function):
                               bg if bg is not None else s.vm)
         ctx.glob_scale = float(glob_scale)
         ctx.fold_aabb = bool(opts.fold_aabb)
+        ctx.vm_shape = tuple(viewmat.shape)
         ctx.set_materialize_grads(False)  # unused outputs' gradients stay None (no zero tensors)
         return outputs
 
@@ -712,6 +763,13 @@ class _TextureGaussians(torch.autograd.Function):
             v_quats=ptr(v_quats), v_rgbs=ptr(v_rgbs), v_opacities=ptr(v_opac), v_centers=ptr(v_centers),
             v_uv0=ptr(v_uv0))
         _launch("gstex_raster_setup_bwd", ctypes.byref(sb), st)
+        v_vm = None
+        if ctx.needs_input_grad[_RASTER_ARGS.index("viewmat")]:
+            # camera pose refinement: the per-splat sums are still in `partials`; chained to the 12 view-matrix entries
+            v_vm = _viewmat_grad_like(
+                _viewmat_bwd(n, ctx.glob_scale, scene.cam, means, scales, quats, row_floats=row_floats,
+                             fold_aabb=ctx.fold_aabb, n_rows=sb.n_rows, nth=nth, offsets=offsets, partials=partials,
+                             row_flags=row_flags), ctx.vm_shape)
         v_bg = None
         if ctx.needs_input_grad[_RASTER_ARGS.index("background")]:
             v_bg = (v_img * state[..., 0:1]).sum((0, 1)) if v_img is not None else torch.zeros_like(bg)
@@ -719,7 +777,7 @@ class _TextureGaussians(torch.autograd.Function):
             v_centers = None  # already chained through the AABB centre into v_means / v_scales / v_quats
         grads = [None] * len(_RASTER_ARGS)
         for name, g in dict(centers=v_centers, rgbs=v_rgbs, opacities=v_opac, means=v_means, scales=v_scales,
-                            quats=v_quats, uv0=v_uv0, texture=v_texture, background=v_bg).items():
+                            quats=v_quats, uv0=v_uv0, texture=v_texture, background=v_bg, viewmat=v_vm).items():
             grads[_RASTER_ARGS.index(name)] = g  # (a name forward does not take raises)
         return tuple(grads)
 
@@ -777,6 +835,15 @@ def texture_gaussians(texture_info, texture_dims, centers, extents, depths, num_
     Returns (img (H,W,3), depth (H,W), reg (H,W), alpha (H,W), tex_img (H,W,C), normal (H,W,3)).
     Gradients flow to rgbs, opacities, means, scales, quats, texture, centers (-> get_aabb_2d),
     uv0 and background; umap/vmap are treated as constants (detached by the caller, gstex.py:977-984).
+
+    Camera pose refinement (not in the reference's rasterizer; gsplat's v_viewmat): when `viewmat` requires a
+    gradient, the backward also returns dL/d(viewmat), its 12 read entries as free variables (gstex_raster_viewmat_bwd:
+    one more launch after the splat chain, deterministic), including with fold_aabb=True the part through the AABB
+    centres; without fold_aabb that part reaches viewmat through get_aabb_2d's own backward.  `c2w` never receives a
+    gradient: the raster reads the camera position only to decide the normal's orientation sign and which splats are
+    near edge-on, and decisions carry no gradient (the view-dependent colour's dependence on the camera position is
+    spherical_harmonics' viewdirs gradient).  A call in which viewmat does not require a gradient launches nothing
+    new.
     """
     if use_torch_impl:
         raise NotImplementedError(
@@ -838,23 +905,42 @@ class _SH(torch.autograd.Function):
         _check(K >= num_sh_bases(degree), f"coeffs has {K} bases < (degree+1)^2 = {num_sh_bases(degree)}")
         out = torch.empty((n, 3), device=coeffs.device, dtype=torch.float32)
         call("gstex_sh_fwd", n, int(degree), K, ptr(viewdirs), ptr(coeffs), ptr(out), _stream(coeffs))
-        ctx.save_for_backward(viewdirs)
+        if ctx.needs_input_grad[1]:  # camera pose refinement: the direction gradient reads the coefficients
+            ctx.save_for_backward(viewdirs, coeffs)
+        else:
+            ctx.save_for_backward(viewdirs)
         ctx.degree, ctx.K = int(degree), K
         return out
 
     @staticmethod
     def backward(ctx, v_out):
-        (viewdirs,) = ctx.saved_tensors
+        viewdirs = ctx.saved_tensors[0]
         n = viewdirs.shape[0]
-        v_coeffs = torch.empty((n, ctx.K, 3), device=viewdirs.device, dtype=torch.float32)
-        call("gstex_sh_bwd", n, ctx.degree, ctx.K, ptr(viewdirs), ptr(v_out.contiguous()), ptr(v_coeffs),
-             _stream(viewdirs))
-        return None, None, v_coeffs
+        v_out = v_out.contiguous()
+        v_coeffs = None
+        if ctx.needs_input_grad[2]:
+            v_coeffs = torch.empty((n, ctx.K, 3), device=viewdirs.device, dtype=torch.float32)
+            call("gstex_sh_bwd", n, ctx.degree, ctx.K, ptr(viewdirs), ptr(v_out), ptr(v_coeffs), _stream(viewdirs))
+        v_dirs = None
+        if ctx.needs_input_grad[1]:
+            v_dirs = sh_dirs_bwd(ctx.degree, 0, viewdirs, ctx.saved_tensors[1], v_out)
+        return None, v_dirs, v_coeffs
+
+
+def sh_dirs_bwd(degree: int, k0: int, viewdirs, coeffs, v_colors) -> torch.Tensor:
+    """gstex_sh_dirs_bwd: the view-direction gradient (N, 3) of spherical_harmonics (k0 = 0, coeffs (N, K, 3)) or of
+    activations.sh_rest (k0 = 1, the DC-less rest coefficients), for checked contiguous fp32 HIP tensors."""
+    n = viewdirs.shape[0]
+    v_dirs = torch.empty((n, 3), device=viewdirs.device, dtype=torch.float32)
+    _launch("gstex_sh_dirs_bwd", n, int(degree), int(k0), coeffs.shape[1], ptr(viewdirs), ptr(coeffs), ptr(v_colors),
+            ptr(v_dirs), _stream(viewdirs))
+    return v_dirs
 
 
 def spherical_harmonics(degrees_to_use: int, viewdirs: torch.Tensor, coeffs: torch.Tensor) -> torch.Tensor:
     """View-dependent colour sum_k basis_k(dir) coeffs[:, k] (no +0.5, gstex.py:1099-1114).
-    Differentiable w.r.t. coeffs only (the caller detaches viewdirs)."""
+    Differentiable w.r.t. coeffs, and w.r.t. viewdirs when they require a gradient (the reference detaches them; camera
+    pose refinement does not: the gradient is that of the forward, which evaluates the basis at viewdirs / |viewdirs|)."""
     return _SH.apply(int(degrees_to_use), viewdirs, coeffs)
 
 

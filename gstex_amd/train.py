@@ -14,7 +14,7 @@ import math
 import torch
 
 # configs/gstex_configs.py.  lrs: the optimizers' lr per group; xyz_lr_final / xyz_max_steps: the means'
-# ExponentialDecaySchedulerConfig (the only scheduled group besides camera_opt, which is not built here); max_steps:
+# ExponentialDecaySchedulerConfig (the only scheduled group besides camera_opt: gstex_amd.pose.PoseRefiner); max_steps:
 # max_num_iterations.  Every preset has sh_degree 3, build_chart_every 100 and sigma_factor 3.
 _COMMON_LRS = {"features_dc": 0.0025, "features_rest": 0.0025 / 20, "opacity": 0.05, "scaling": 0.005,
                "rotation": 0.001, "texture_dc": 1e-3}
@@ -61,7 +61,7 @@ def _to_device(pair, device):
 
 
 def fit(trainer, pairs, steps: int, *, xyz_lr_final: float | None = None, max_steps: int = 15000,
-        build_chart_every: int = 100, seed: int = 0, on_step=None) -> dict:
+        build_chart_every: int = 100, seed: int = 0, on_step=None, pose_refiner=None) -> dict:
     """Run `steps` training steps from trainer.step on.  pairs: a sequence of (View, image[, mask]) as
     gstex_amd.data.load_blender yields them, moved to the trainer's device once.  Per step s = trainer.step:
 
@@ -71,6 +71,10 @@ def fit(trainer, pairs, steps: int, *, xyz_lr_final: float | None = None, max_st
     3. zero_grad(), forward_backward(), optimizer_step();
     4. recharge() when s % build_chart_every == 0 (gstex.py:907-914; 0 or None: never);
     5. on_step(s, out) with forward_backward's StepOutput.
+
+    pose_refiner (a gstex_amd.pose.PoseRefiner over these pairs; the presets' camera_opt group): step 3 renders
+    pose_refiner.view(k, view) for the chosen pair k, adds pose_refiner.regulariser() to the loss and calls
+    pose_refiner.step() after optimizer_step().  None: the loop above, unchanged.
 
     Returns loss (a (steps,) device tensor, filled without a read-back), views (the chosen indices) and recharts
     (the steps s after which a rechart ran).  The only host synchronisation is inside a rechart (build_charts'
@@ -92,8 +96,14 @@ def fit(trainer, pairs, steps: int, *, xyz_lr_final: float | None = None, max_st
         k = order.pop()
         view, image, mask = pairs[k]
         trainer.zero_grad()
-        out = trainer.forward_backward(view, image, mask)
-        trainer.optimizer_step()
+        if pose_refiner is None:
+            out = trainer.forward_backward(view, image, mask)
+            trainer.optimizer_step()
+        else:
+            out = trainer.forward_backward(pose_refiner.view(k, view), image, mask,
+                                           extra_loss=pose_refiner.regulariser())
+            trainer.optimizer_step()
+            pose_refiner.step()
         losses[i].copy_(out.loss)
         views.append(k)
         if build_chart_every and s % build_chart_every == 0:

@@ -341,11 +341,58 @@ typedef struct gstex_raster_setup_bwd_args {
 } gstex_raster_setup_bwd_args;
 int gstex_raster_setup_bwd(const gstex_raster_setup_bwd_args* args, void* stream);
 
+/* The raster's view-matrix gradient -- added within ABI 19 (additive).  v_viewmat[3][4] = dL/d(cam.viewmat), its 12
+ * entries taken as free variables (gsplat's v_viewmat; no orthonormality constraint is applied), OVERWRITTEN.
+ * The render depends on V = [R|t] only through each splat's camera-space vectors W0 = R (su t_u), W1 = R (sv t_v),
+ * W2 = R mu + t, so  dL/dV[r][:3] = sum_i dW0_r a_i + dW1_r b_i + dW2_r mu_i  and  dL/dV[r][3] = sum_i dW2_r.  The
+ * texture-affine sums and the normal sum of the rows take no part: umap / vmap and the normal are world-space.
+ *   Raster mode (partials != NULL): call it after gstex_raster_setup_bwd, with that call's n, glob_scale, row_floats,
+ * fold_aabb, n_rows, cam, means, scales, quats, num_tiles_hit, offsets, partials and row_flags (read for NULL-ness
+ * only: NULL = the (n, row_floats) accumulator, row g; else the sums gstex_raster_setup_bwd wrote over each splat's
+ * first row).  partials is read, not consumed.  fold_aabb: the rows' centre gradient is chained through the AABB
+ * centre (gstex_aabb_2d on these splats) and added.  A splat without pairs contributes zero, and so does every splat
+ * when n_rows >= 0 and offsets[n] > n_rows.  v_centers must be NULL.
+ *   Centre-only mode (partials == NULL): v_centers[n][2] is chained through the AABB centre alone -- the viewmat
+ * gradient of gstex_aabb_2d; num_tiles_hit / offsets / row_flags / row_floats / n_rows / fold_aabb are not read.
+ * Culled splats (centre = extent = 0 in gstex_aabb_2d) contribute zero.
+ *   The chain is evaluated in fp64, one thread per splat; the sum is deterministic and in two stages: each block of 256
+ * splats reduces its 12 values in fp64 into row b of workspace, one final block sums the rows in a fixed order (no
+ * atomics: the same inputs give the same bits).  workspace: gstex_raster_viewmat_bwd_workspace(n) bytes =
+ * ceil(n / 256) * 12 doubles, 8-byte aligned, caller-owned scratch.  No allocation, no synchronisation. */
+typedef struct gstex_raster_viewmat_bwd_args {
+    int32_t n;
+    float glob_scale;
+    int32_t row_floats;
+    int32_t fold_aabb;
+    int64_t n_rows;
+    gstex_camera cam;
+    const float* means;
+    const float* scales;
+    const float* quats;
+    const int32_t* num_tiles_hit;
+    const int32_t* offsets;
+    const float* partials;
+    const uint32_t* row_flags;
+    const float* v_centers;
+    double* workspace;
+    float* v_viewmat;
+} gstex_raster_viewmat_bwd_args;
+size_t gstex_raster_viewmat_bwd_workspace(int32_t n);
+int gstex_raster_viewmat_bwd(const gstex_raster_viewmat_bwd_args* args, void* stream);
+
 /* ---- spherical harmonics (degree <= 4) ------------------------------------------------- */
 int gstex_sh_fwd(int32_t n, int32_t degree, int32_t n_coeffs, const float* viewdirs,
                  const float* coeffs, float* colors, void* stream);
 int gstex_sh_bwd(int32_t n, int32_t degree, int32_t n_coeffs, const float* viewdirs,
                  const float* v_colors, float* v_coeffs, void* stream);
+/* The view-direction gradient of gstex_sh_fwd / gstex_sh_rest_fwd -- added within ABI 19 (additive).
+ * v_viewdirs[i] = sum_{k, c} v_colors[i][c] * coeffs[i][k][c] * dY_k/d(viewdirs[i]) over the active degree's bases,
+ * OVERWRITTEN.  k0 = 0: coeffs[n][n_coeffs][3] holds bases 0 .. n_coeffs - 1 (gstex_sh_fwd's layout); k0 = 1: the
+ * DC-less rest layout of gstex_sh_rest_fwd (row k holds basis k + 1).  Y_k is what the forward evaluates: the basis
+ * polynomial at viewdirs[i] / |viewdirs[i]| for degree >= 1, so the result is tangential (the polynomial's gradient
+ * with its radial part removed, divided by |viewdirs[i]|); degree 0 gives zero.  Evaluated in fp64 per splat. */
+int gstex_sh_dirs_bwd(int32_t n, int32_t degree, int32_t k0, int32_t n_coeffs, const float* viewdirs,
+                      const float* coeffs, const float* v_colors, float* v_viewdirs, void* stream);
 
 /* ---- jagged texture resample ------------------------------------------------------------ */
 int gstex_texture_sample(int64_t n_query, int32_t channels, const int32_t* query_dims,
