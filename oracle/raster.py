@@ -397,7 +397,7 @@ def rasterize(inp: RasterInputs, grad_dtype=F64, bins=None, table_dtype=None):
     dec = _render(inp, F32, tile_ranges, sorted_ids, None)
     hi = _render(inp, grad_dtype, tile_ranges, sorted_ids, dec["decisions"], table_dtype=table_dtype)
     aux = dict(offsets=offsets, tile_ranges=tile_ranges, sorted_ids=sorted_ids, sorted_slots=sorted_slots,
-               last=dec["last"], T_final=dec["out"]["T_final"], margin=dec["margin"])
+               last=dec["last"], T_final=dec["out"]["T_final"], margin=dec["margin"], decisions=dec["decisions"])
     return dec["out"], hi["out"], aux
 
 
@@ -641,8 +641,9 @@ def _render(inp: RasterInputs, dtype, tile_ranges, sorted_ids, decisions, edit=N
         last_all.append(last)
         margin_all.append(margin if decisions is None else torch.full((P,), float("inf")))
         if new_dec is not None:
+            # near_skip (test support, never read back): the pairs the traversal reaches and skips for z < near
             new_dec["tiles"][t] = dict(nz=nz, use3=use3, aclamp=aclamp, incl=incl, in_u=in_u, in_v=in_v,
-                                       i0=i0, j0=j0)
+                                       i0=i0, j0=j0, ids=ids, near_skip=nz & ~(zz >= near) & (kidx < first[None, :]))
 
     Np = H * W
     out = {}

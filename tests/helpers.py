@@ -1,12 +1,15 @@
 """Shared case builders: one seeded synthetic case evaluated by the CPU oracle and by the HIP path."""
 from __future__ import annotations
 
+import dataclasses
+import math
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
-from gstex_amd.scene import make_scene, sphere_view
+from gstex_amd.charts import build_charts
+from gstex_amd.scene import CAM_RADIUS, Scene, make_scene, sphere_view
 from oracle import raster as O
 
 TOL_ABS = 1e-5  # forward parity tolerance (fp32), north_star: "within 1e-5 fp32"
@@ -23,10 +26,35 @@ class Case:
     flip_mask: torch.Tensor = None  # set by oracle_run: pixels excluded from gradient comparisons
 
 
+def anisotropic(scene: Scene, ratio, seed, n_texels) -> Scene:
+    """The scene with each splat's two in-plane scales pulled apart: s_u *= e^r, s_v *= e^-r, r uniform in
+    +-log(ratio) / 2 (s_u / s_v within [1 / ratio, ratio], the product s_u s_v kept), recharted for the new scales
+    (non-square h x w blocks) with fresh texels.  Seeded on its own generator (seed + 77).  ratio <= 1: the scene as
+    it is."""
+    if ratio <= 1.0:
+        return scene
+    g = torch.Generator().manual_seed(seed + 77)
+    r = (torch.rand(scene.n, generator=g) * 2 - 1) * math.log(ratio) / 2
+    log_scales = scene.log_scales.clone()
+    log_scales[:, 0] += r
+    log_scales[:, 1] -= r
+    if n_texels and n_texels > 0:
+        dims, mappings, ps = build_charts(log_scales, float(n_texels))
+        T = int((dims[:, 0] * dims[:, 1]).sum().item())
+        texture = torch.rand((T, scene.texture.shape[1]), generator=g)
+    else:  # 2DGS mode (make_scene): no blocks, the mappings follow the scales
+        dims, texture, ps = scene.texture_dims, scene.texture, scene.pixel_scale
+        mappings = torch.stack([1 / (6.0 * torch.exp(log_scales[:, 0])), 1 / (6.0 * torch.exp(log_scales[:, 1]))], -1)
+    return dataclasses.replace(scene, log_scales=log_scales, texture_dims=dims, mappings=mappings, texture=texture,
+                               pixel_scale=ps)
+
+
 def make_case(n=300, n_texels=20000, H=64, W=80, seed=0, view=0, opacity=None, C=3,
-              settings=(1 << 9) | (1 << 10), bg=None, cube=2.0, glob_scale=1.0):
-    sc = make_scene(n, n_texels, channels=C, seed=seed, opacity=opacity, cube=cube)
-    v = sphere_view(view, H, W)
+              settings=(1 << 9) | (1 << 10), bg=None, cube=2.0, glob_scale=1.0, *, aniso=1.0, radius=CAM_RADIUS):
+    """aniso > 1: the scene through anisotropic(); radius: the camera's distance from the centre of the +-cube/2 cube
+    the splats fill (below ~1.7 the near plane and the camera plane cut into the scene)."""
+    sc = anisotropic(make_scene(n, n_texels, channels=C, seed=seed, opacity=opacity, cube=cube), aniso, seed, n_texels)
+    v = sphere_view(view, H, W, radius=radius)
     means, scales, quats, opac = sc.activated()
     cam = O.Camera(v.viewmat, v.fx, v.fy, v.cx, v.cy, H, W, 16, v.c2w[:3, 3])
     centers, extents = O.aabb_2d(means, scales, glob_scale, quats, cam)
@@ -124,6 +152,62 @@ def gpu_run(case: Case, grads=True, seed=5, device="cuda", outputs=None):
 
 FLIP_MARGIN = 1e-5  # relative distance from a threshold within which an fp32 decision may flip (exp/rcp ulps)
 FLIP_FRACTION = 1e-3  # at most this fraction of the pixels (and at least 4) may carry a flipped decision
+
+
+# Cases outside the random-init distribution of make_scene (isotropic splats, square charts, a camera 2.7 away from
+# the nearest splat, glob_scale 1): anisotropic splats on non-square charts, glob_scale != 1, cameras close to and
+# inside the +-1 cube.  Fixed inputs; check_stress asserts, from the oracle's run alone, that each reaches its regime.
+# Seeds tried: the ones below only (every condition of check_stress held at the first seed of each row).
+STRESS_CASES = {
+    "aniso4": dict(n=150, n_texels=6000, H=48, W=48, seed=3, aniso=4),
+    "aniso10_glob": dict(n=150, n_texels=6000, H=48, W=48, seed=5, aniso=10, glob_scale=1.4, opacity=None),
+    "glob0.6": dict(n=150, n_texels=6000, H=48, W=48, seed=6, glob_scale=0.6),
+    "near1.3": dict(n=300, n_texels=8000, H=48, W=48, seed=7, radius=1.3, opacity=None),
+    "inside0.5_aniso4": dict(n=300, n_texels=8000, H=48, W=48, seed=8, radius=0.5, aniso=4, opacity=None),
+    "2dgs_near": dict(n=300, n_texels=0, H=48, W=48, seed=9, radius=1.0),
+}
+STRESS_ANISO = ("aniso4", "aniso10_glob", "inside0.5_aniso4")
+STRESS_NEAR = ("near1.3", "inside0.5_aniso4", "2dgs_near")
+
+
+def cull_classes(inp):
+    """The oracle's preprocessing classes of every splat (preprocess.hip's branches, from oracle values alone):
+    near: Tw.z <= near; crossing: not near, and the 3-sigma disc reaches the camera plane (d >= 0); clipped: centre
+    depth <= 0.01 (project_points writes xy = 0)."""
+    _, _, Tw = O.splat_homography(inp.means, inp.scales, inp.glob_scale, inp.quats, inp.cam)
+    c9 = float(O.K_CUTOFF2)
+    d = (c9 * (Tw[:, 0] * Tw[:, 0]) + c9 * (Tw[:, 1] * Tw[:, 1])) - Tw[:, 2] * Tw[:, 2]
+    near = Tw[:, 2] <= float(O.K_NEAR)
+    return dict(near=near, crossing=~near & (d >= 0), clipped=inp.depths <= float(O.K_PROJ_CLIP))
+
+
+def check_stress(name, case, aux):
+    """The stress case reaches the regime it is named for: facts of the oracle's run, not of the code under test."""
+    inp = case.inp
+    n = inp.means.shape[0]
+    seen = torch.zeros(n, dtype=torch.bool)  # splats on some tile list
+    seen[torch.as_tensor(aux["sorted_ids"]).long()] = True
+    h, w = inp.texture_dims[:, 0].long(), inp.texture_dims[:, 1].long()
+    if name in STRESS_ANISO:
+        assert int((h != w).sum()) * 2 >= n, f"{name}: only {int((h != w).sum())} / {n} non-square charts"
+        assert bool((seen & ((h > 2 * w) | (w > 2 * h))).any()), f"{name}: no visible chart beyond 2:1"
+    if name in STRESS_NEAR:
+        cls = cull_classes(inp)
+        assert bool(cls["near"].any()), f"{name}: no splat culled by Tw.z <= near"
+        assert bool(cls["crossing"].any()), f"{name}: no splat culled by d >= 0"
+        assert not bool((seen & (cls["near"] | cls["crossing"])).any())
+        skipped = torch.zeros(n, dtype=torch.bool)  # splats with a reached pair skipped for z < near ...
+        included = torch.zeros(n, dtype=torch.bool)  # ... and with a pair that contributes
+        for d in aux["decisions"]["tiles"].values():
+            skipped[d["ids"][d["near_skip"].any(1)]] = True
+            included[d["ids"][d["incl"].any(1)]] = True
+        assert bool((skipped & included).any()), f"{name}: no splat with one pair skipped for z < near, another kept"
+        if name == "inside0.5_aniso4":
+            assert bool(cls["clipped"].any()), f"{name}: no centre with z <= 0.01"
+    assert float(aux["T_final"].detach().min()) < 0.5, f"{name}: alpha.max() <= 0.5"
+    H, W = inp.cam.H, inp.cam.W
+    near_flip = int((aux["margin"] < FLIP_MARGIN).sum())
+    assert near_flip <= max(4, FLIP_FRACTION * H * W), f"{name}: {near_flip} pixels within FLIP_MARGIN of a threshold"
 
 
 def assert_close_fwd(gpu, ref64, names=("img", "depth", "reg", "alpha", "tex", "normal"), margin=None):

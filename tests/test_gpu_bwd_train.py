@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from gstex_amd.scene import make_scene, sphere_view
-from helpers import DIFF, FLIP_MARGIN, GRAD_RTOL, Case, grad_norm_err, make_case
+from helpers import DIFF, FLIP_MARGIN, GRAD_RTOL, STRESS_CASES, Case, check_stress, grad_norm_err, make_case
 from oracle import raster as O
 
 pytestmark = pytest.mark.gpu
@@ -79,8 +79,14 @@ def _near_edge_on():
     return make_case(n=40, n_texels=2500, H=40, W=56, seed=35)
 
 
+# outside the random-init distribution (helpers.STRESS_CASES): anisotropic splats on non-square charts with glob_scale
+# 1.4; a camera at the edge of the splat cube (near-plane culls, per-pair z < near skips)
+STRESS = {"aniso": "aniso10_glob", "near": "near1.3"}
+
 SCENES = {"partial_tiles": _partial_tiles, "deep_list": _deep_list, "large_block": _large_block,
-          "untextured": _untextured, "near_edge_on": _near_edge_on}
+          "untextured": _untextured, "near_edge_on": _near_edge_on,
+          "aniso": lambda: make_case(**STRESS_CASES[STRESS["aniso"]]),
+          "near": lambda: make_case(**STRESS_CASES[STRESS["near"]])}
 
 
 def _check_scene(name, case, aux):
@@ -100,6 +106,8 @@ def _check_scene(name, case, aux):
         assert bool((seen & (hw == 0)).any()) and bool((seen & (hw > 0)).any())
     elif name == "near_edge_on":
         assert bool((seen & O._splat_table(inp, torch.float64)["hp"]).any())
+    elif name in STRESS:
+        check_stress(STRESS[name], case, aux)
 
 
 _ORACLE: dict = {}

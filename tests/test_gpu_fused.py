@@ -9,11 +9,16 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def _setup(n=4000, texels=80_000, res=96):
+def _setup(n=4000, texels=80_000, res=96, aniso=1.0):
+    """aniso > 1: the scene through helpers.anisotropic (s_u != s_v, non-square charts) before the trainer takes it."""
     from gstex_amd.scene import make_scene, sphere_view
+    from helpers import anisotropic
 
     dev = torch.device("cuda", 0)
-    sc = make_scene(n, texels, seed=5)
+    sc = anisotropic(make_scene(n, texels, seed=5), aniso, 5, texels)
+    if aniso > 1.0:
+        h, w = sc.texture_dims[:, 0], sc.texture_dims[:, 1]
+        assert int((h != w).sum()) * 2 >= n and bool(((h > 2 * w) | (w > 2 * h)).any())
     views = [sphere_view(i, res, res).to(dev) for i in range(3)]
     g = torch.Generator().manual_seed(2)
     gts = [torch.rand((res, res, 3), generator=g).to(dev) for _ in range(3)]
@@ -39,10 +44,19 @@ def test_fused_render_matches_per_op(monkeypatch, n, texels, start):
     """n = 4000: several scan tiles with a partial last one; 1500: one full tile and a partial one; 300: a single
     partial block of the fused preprocessing kernel and a single scan tile.  start 1500: SH degree 1 of the ramp;
     start 0: degree 0, which gstex_train_prologue runs through the per-op entry points."""
+    _check_fused_render(monkeypatch, n, texels, start)
+
+
+def test_fused_render_matches_per_op_anisotropic(monkeypatch):
+    """s_u / s_v within [1/10, 10] on non-square charts: the per-axis scale chain of the fused prologue and epilogue."""
+    _check_fused_render(monkeypatch, 300, 6_000, 3000, aniso=10.0)
+
+
+def _check_fused_render(monkeypatch, n, texels, start, aniso=1.0):
     from gstex_amd.model import GStexTrainer
 
     calls = _count_fused(monkeypatch)
-    dev, sc, views, gts = _setup(n, texels)
+    dev, sc, views, gts = _setup(n, texels, aniso=aniso)
     tr = GStexTrainer(sc, dev, start_step=start, defer_texture=True, fused_step=True)
     # the first render sizes the pair capacity (one read-back) through the per-op path
     tr.zero_grad()
@@ -142,13 +156,20 @@ def test_fused_step_with_gradsync_trains_like_per_op(monkeypatch):
 def test_epilogue_matches_per_op_entry_points():
     """gstex_train_epilogue (setup bwd + activation bwd + SH rest bwd in one kernel) writes bit-identical gradients to
     gstex_raster_setup_bwd (fold_aabb) -> gstex_activate_bwd / gstex_sh_rest_bwd on the same accumulator rows."""
+    _check_epilogue(*_setup(1500, 30_000))
+
+
+def test_epilogue_matches_per_op_entry_points_anisotropic():
+    _check_epilogue(*_setup(300, 6_000, aniso=10.0))
+
+
+def _check_epilogue(dev, sc, views, _):
     import ctypes
 
     from gstex_amd import _lib, ops
     from gstex_amd.activations import activate
     from gstex_amd.model import GStexTrainer
 
-    dev, sc, views, _ = _setup(1500, 30_000)
     tr = GStexTrainer(sc, dev, start_step=3000, defer_texture=True)
     view = views[1]
     with torch.no_grad():

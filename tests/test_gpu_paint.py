@@ -42,9 +42,10 @@ def strokes(H, W, seed):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_case(seed, H=64, W=80, n=400, n_texels=30000, opacity=0.1):
-    """One seeded case with the oracle's depth and the oracle's edit sums for both strokes (computed once)."""
-    case = make_case(n=n, n_texels=n_texels, H=H, W=W, seed=seed, settings=EDIT, opacity=opacity)
+def oracle_case(seed, H=64, W=80, n=400, n_texels=30000, opacity=0.1, aniso=1.0):
+    """One seeded case with the oracle's depth and the oracle's edit sums for both strokes (computed once).  aniso: the
+    scene through helpers.anisotropic (non-square texel blocks)."""
+    case = make_case(n=n, n_texels=n_texels, H=H, W=W, seed=seed, settings=EDIT, opacity=opacity, aniso=aniso)
     inp = case.inp
     depth = O.rasterize(inp)[0]["depth"]  # the caller's depth render (gstex.py:567)
     f32, canvas = strokes(H, W, seed)
@@ -105,6 +106,23 @@ def test_scatter_matches_oracle(seed, variant):
     # a transparent pixel adds the weight channel only: texels reached by nothing else have wt > 0 and a == 0
     assert int(((ref[:, 4] > 0) & (ref[:, 3] == 0)).sum()) > 0
     assert torch.equal(got.cpu()[:, 3] > 0, ref[:, 3] > 0)
+
+
+def test_scatter_matches_oracle_anisotropic():
+    """s_u / s_v within [1/10, 10], h x w blocks up to 10 : 1: the scatter's texel addressing (off + i w + j, x against
+    h, y against w) where h != w.  Random opacities (opacity=None): at the other cases' 0.1 this small scene's depth
+    render lies within 1e-2 of almost no pair's depth and the stroke reaches 24 texels (total weight 0.16); here 574.
+    One seed tried."""
+    case, depth, f32, _, ref, _ = oracle_case(33, H=48, W=48, n=150, n_texels=6000, opacity=None, aniso=10.0)
+    h, w = case.inp.texture_dims[:, 0].long(), case.inp.texture_dims[:, 1].long()
+    seen = torch.zeros(h.numel(), dtype=torch.bool)
+    inp = case.inp
+    seen[torch.as_tensor(O.bin_and_sort(inp.centers, inp.extents, inp.depths, 48, 48)[2]).long()] = True
+    assert int((h != w).sum()) * 2 >= h.numel() and bool((seen & ((h > 2 * w) | (w > 2 * h))).any())
+    painted = ref[:, 4] > 0  # the stroke reaches texels of blocks beyond 2 : 1
+    ids = torch.repeat_interleave(torch.arange(h.numel()), h * w)
+    assert bool((painted & ((h > 2 * w) | (w > 2 * h))[ids]).any())
+    assert_same_sums(gpu_scatter(case, f32, depth), ref, "anisotropic seed 33 f32 vs oracle")
 
 
 def test_hp_marks_do_not_change_the_scatter_decisions():

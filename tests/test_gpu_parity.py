@@ -11,13 +11,18 @@ the oracle's fp64 autograd of the same function:
     intrinsics the kernels receive.  The oracle's own fp32 autograd error is printed beside each result (it is
     the yardstick, no longer part of the bound).  Measured (profiles/r06_parity_hp.log): every gradient of every
     case <= 8.8e-6 norm-wise and <= 4.6e-6 max-element (cfg3 96x96: means / quats 3.0e-6 / 3.3e-6 norm-wise).
+    The cases of helpers.STRESS_CASES (anisotropic splats on non-square charts, glob_scale 1.4 / 0.6, cameras at the
+    edge of and inside the splat cube), all outputs and photometric: every gradient <= 1.31e-6 norm-wise and <= 2.31e-6
+    max-element (aniso4 means, where the oracle's own fp32 autograd reads 2.33e-6), the forward within 2.1e-6 (depth),
+    no flipped pixel; against the world-space restatement directly (aniso10_glob) <= 8.7e-7 / 1.02e-6.  No case takes
+    an allowance over GRAD_RTOL.
 """
 import numpy as np
 import pytest
 import torch
 
-from helpers import DIFF, GRAD_RTOL, assert_close_fwd, gpu_run, grad_norm_err, grad_rel_err, make_case, \
-    oracle_run, upstream
+from helpers import DIFF, FLIP_MARGIN, GRAD_RTOL, STRESS_CASES, assert_close_fwd, check_stress, cull_classes, \
+    gpu_run, grad_norm_err, grad_rel_err, make_case, oracle_run, upstream
 from oracle import raster as O
 
 pytestmark = pytest.mark.gpu
@@ -55,6 +60,47 @@ def test_project_points_and_aabb_match_oracle():
 
     d2, c2, e2, n2 = ops.preprocess(inp.means.to(DEV), inp.scales.to(DEV), 1, inp.quats.to(DEV), v.viewmat.to(DEV),
                                     intr, 100, 120)
+    assert torch.equal(d2.cpu(), odep) and torch.equal(c2, c) and torch.equal(e2, e) and torch.equal(n2, nth)
+
+
+NEAR_CASES = ["near1.3", "inside0.5_aniso4"]
+
+
+@pytest.mark.parametrize("name", NEAR_CASES)
+def test_preprocess_near_camera_matches_oracle(name):
+    """A camera at the edge of / inside the splat cube: splats at or behind the near plane (Tw.z <= near), discs that
+    cross the camera plane (d >= 0) and centres behind the projection clip (z <= 0.01) sit among visible ones.  The
+    equalities of test_project_points_and_aabb_match_oracle, and every cull class (the oracle's) written as zeros."""
+    import gstex_cuda
+    from gstex_amd import ops
+
+    case = make_case(**STRESS_CASES[name])
+    v, inp, cam = case.view, case.inp, case.inp.cam
+    H, W, glob = cam.H, cam.W, inp.glob_scale
+    intr = (v.fx, v.fy, v.cx, v.cy)
+    cls = cull_classes(inp)
+    culled = cls["near"] | cls["crossing"]
+    counts = {k: int(m.sum()) for k, m in cls.items()}
+    print(f"[parity] {name} cull classes: {counts}, visible {int((case.nth > 0).sum())} / {culled.numel()}")
+    assert counts["near"] > 0 and counts["crossing"] > 0 and int((~culled).sum()) > 0
+    assert counts["clipped"] > 0 or name != "inside0.5_aniso4"
+    xys, depths = gstex_cuda.project_points(inp.means.to(DEV), v.viewmat.to(DEV), intr)
+    oxy, odep = O.project_points(inp.means, cam)
+    assert torch.equal(depths.cpu(), odep), "depths not bit-exact"
+    assert (xys.cpu() - oxy).abs().max().item() <= 1e-6 * max(1.0, oxy.abs().max().item())
+    assert float(xys.cpu()[cls["clipped"]].abs().sum()) == 0.0, "a clipped centre projects to (0, 0)"
+    c, e = gstex_cuda.get_aabb_2d(inp.means.to(DEV), inp.scales.to(DEV), glob, inp.quats.to(DEV), v.viewmat.to(DEV),
+                                  intr)
+    oc, oe = O.aabb_2d(inp.means, inp.scales, glob, inp.quats, cam)
+    assert torch.equal(c.cpu(), oc.detach()), f"centers not bit-exact: {(c.cpu() - oc).abs().max()}"
+    assert torch.equal(e.cpu(), oe), f"extents not bit-exact: {(e.cpu() - oe).abs().max()}"
+    assert float(c.cpu()[culled].abs().sum()) == 0.0 and float(e.cpu()[culled].abs().sum()) == 0.0
+    assert float(e.cpu()[~culled].min()) > 0.0
+    nth = gstex_cuda.get_num_tiles_hit_2d(c, e, H, W, 16)
+    assert torch.equal(nth.cpu(), O.num_tiles_hit(oc, oe, H, W)) and torch.equal(nth.cpu(), case.nth)
+    assert int(nth.cpu()[culled].sum()) == 0 and int((nth > 0).sum()) > 0
+    d2, c2, e2, n2 = ops.preprocess(inp.means.to(DEV), inp.scales.to(DEV), glob, inp.quats.to(DEV), v.viewmat.to(DEV),
+                                    intr, H, W)
     assert torch.equal(d2.cpu(), odep) and torch.equal(c2, c) and torch.equal(e2, e) and torch.equal(n2, nth)
 
 
@@ -111,6 +157,19 @@ def test_binning_bit_exact():
     case = make_case(n=3000, n_texels=0, H=96, W=112, seed=5)
     tr = _bins_equal(case)
     assert (tr[:, 1] - tr[:, 0]).max() > 0
+
+
+@pytest.mark.parametrize("name", NEAR_CASES)
+def test_binning_near_camera_bit_exact(name):
+    # culled splats (no tiles) between visible ones in id order, depths down to the near plane in the sort key
+    case = make_case(**STRESS_CASES[name])
+    tr = _bins_equal(case)
+    vis = case.nth > 0
+    assert 0 < int(vis.sum()) < vis.numel() and (tr[:, 1] - tr[:, 0]).max() > 0
+    assert bool((~vis[:-1] & vis[1:]).any()) and bool((vis[:-1] & ~vis[1:]).any())
+    assert float(case.inp.depths[vis].min()) < 0.3 and float(case.inp.depths[~vis].min()) < 0.2
+    if name == "inside0.5_aniso4":  # splats behind the camera: negative depths (sign bit set) among the inputs
+        assert float(case.inp.depths[~vis].min()) < 0.0
 
 
 def test_binning_many_tiles_global_count_path():
@@ -170,9 +229,24 @@ def test_raster_backward_photometric_only(name):
     _check_raster(name, ("img", "alpha", "tex"))
 
 
+# The cases of helpers.STRESS_CASES: anisotropic splats on non-square charts (the h / w and s_u / s_v roles), glob_scale
+# != 1, the near-plane cull and the per-pair z < near skip.  Same bounds as above; check_stress first asserts, from the
+# oracle's run, that the case reaches its regime.
+@pytest.mark.parametrize("name", list(STRESS_CASES))
+def test_raster_stress_forward_backward(name):
+    _check_raster(name, None)
+
+
+@pytest.mark.parametrize("name", ["aniso10_glob", "near1.3", "inside0.5_aniso4"])
+def test_raster_stress_backward_photometric_only(name):
+    _check_raster(name, ("img", "alpha", "tex"))
+
+
 def _check_raster(name, outputs):
-    case = make_case(**CASES[name])
+    case = make_case(**(STRESS_CASES[name] if name in STRESS_CASES else CASES[name]))
     o32, o64, aux, og = oracle_run(case, grads=True, outputs=outputs)
+    if name in STRESS_CASES:
+        check_stress(name, case, aux)
     gout, gg = gpu_run(case, grads=True, outputs=outputs)
     fwd = {k: (gout[k].double() - o64[k]).abs().max().item() for k in gout}
     _report(f"{name} fwd", fwd)
@@ -190,6 +264,37 @@ def _check_raster(name, outputs):
     for k in DIFF:
         assert norm_errs[k] <= GRAD_RTOL, f"{name}: grad {k} norm-wise rel err {norm_errs[k]:.3e} > {GRAD_RTOL:.0e}"
         assert errs[k] <= GRAD_RTOL, f"{name}: grad {k} max rel err {errs[k]:.3e} > {GRAD_RTOL:.0e}"
+
+
+def test_hip_matches_world_space_restatement():
+    """The kernels against the world-space ray restatement of test_oracle_independent.py directly (not through
+    oracle/raster.py, which is written from the kernels' own formulation), on anisotropic splats with non-square
+    charts and glob_scale 1.4: the forward within the usual tolerance (the oracle supplies only the decision margins),
+    every gradient within GRAD_RTOL of the restatement's float64 autograd."""
+    from test_oracle_independent import OUTPUTS, ray_render_torch
+
+    name = "aniso10_glob"
+    case = make_case(**STRESS_CASES[name])
+    inp = case.inp
+    _, _, aux = O.rasterize(inp)
+    check_stress(name, case, aux)
+    case.flip_mask = aux["margin"] < FLIP_MARGIN
+    leaves = {k: getattr(inp, k).detach().clone().double().requires_grad_(True) for k in DIFF}
+    ref = ray_render_torch(inp, leaves)
+    up = upstream(inp.cam.H, inp.cam.W, case.C, 5, case.flip_mask)
+    sum((ref[k] * up[k].double()).sum() for k in OUTPUTS).backward()
+    gout, gg = gpu_run(case, grads=True)
+    ref = {k: v.detach() for k, v in ref.items()}
+    _report(f"{name} fwd vs restatement", {k: (gout[k].double() - ref[k]).abs().max().item() for k in OUTPUTS})
+    assert_close_fwd(gout, ref, margin=aux["margin"])
+    errs = {k: grad_rel_err(gg[k], leaves[k].grad)[0] for k in DIFF}
+    norm_errs = {k: grad_norm_err(gg[k], leaves[k].grad) for k in DIFF}
+    _report(f"{name} bwd vs restatement max-rel", errs)
+    _report(f"{name} bwd vs restatement norm-rel", norm_errs)
+    for k in DIFF:
+        assert float(leaves[k].grad.abs().max()) > 0, k
+        assert norm_errs[k] <= GRAD_RTOL, f"grad {k} norm-wise rel err {norm_errs[k]:.3e} > {GRAD_RTOL:.0e}"
+        assert errs[k] <= GRAD_RTOL, f"grad {k} max rel err {errs[k]:.3e} > {GRAD_RTOL:.0e}"
 
 
 def test_raster_without_near_edge_on_rows(monkeypatch):
@@ -474,9 +579,21 @@ def test_fused_loss_matches_eager_torch(C):
 # ---------------------------------------------------------------- texture_edit (viewer paint tool, §8f-4)
 @pytest.mark.parametrize("seed", [31, 32])
 def test_texture_edit_matches_oracle(seed):
+    _check_texture_edit(make_case(n=400, n_texels=30000, H=64, W=80, seed=seed, settings=1 << 13), seed)
+
+
+def test_texture_edit_matches_oracle_anisotropic():
+    """Non-square texel blocks and glob_scale 1.4: the scatter's texel addressing (off + i w + j) and its records."""
+    kw = dict(STRESS_CASES["aniso10_glob"], settings=1 << 13)
+    case = make_case(**kw)
+    case.inp.hp = False  # texture_edit's records carry no near-edge-on rows
+    check_stress("aniso10_glob", case, O.rasterize(case.inp)[2])
+    _check_texture_edit(case, kw["seed"])
+
+
+def _check_texture_edit(case, seed):
     import gstex_cuda
 
-    case = make_case(n=400, n_texels=30000, H=64, W=80, seed=seed, settings=1 << 13)
     inp, v = case.inp, case.view
     H, W = inp.cam.H, inp.cam.W
     g = torch.Generator().manual_seed(seed)
@@ -489,9 +606,9 @@ def test_texture_edit_matches_oracle(seed):
     n = inp.means.shape[0]
     out = gstex_cuda.texture_edit(
         (n, 1, 5), dv(inp.texture_dims), dv(rgb), dv(a[..., None]), dv(dlo), dv(dhi), dv(inp.centers),
-        dv(inp.extents), dv(inp.depths), dv(case.nth), dv(inp.opacities), dv(inp.means), dv(inp.scales), 1.0,
-        dv(inp.quats), dv(inp.uv0), dv(inp.umap), dv(inp.vmap), dv(v.viewmat), dv(v.c2w), v.fx, v.fy, v.cx, v.cy,
-        H, W, 16, 1 << 13, background=torch.zeros(3, device=DEV))
+        dv(inp.extents), dv(inp.depths), dv(case.nth), dv(inp.opacities), dv(inp.means), dv(inp.scales),
+        inp.glob_scale, dv(inp.quats), dv(inp.uv0), dv(inp.umap), dv(inp.vmap), dv(v.viewmat), dv(v.c2w), v.fx, v.fy,
+        v.cx, v.cy, H, W, 16, 1 << 13, background=torch.zeros(3, device=DEV))
     got = out.double().cpu()
     assert got.shape == ref.shape
     assert float(ref[:, 4].sum()) > 1.0, "the stroke must reach texels"

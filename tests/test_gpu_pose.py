@@ -13,7 +13,8 @@ from gstex_amd.activations import sh_rest
 from gstex_amd.model import GStexTrainer, _gauss_window
 from gstex_amd.pose import PoseRefiner, corrected_matrices, exp_so3xr3
 from gstex_amd.scene import View, make_scene, sphere_view
-from helpers import DIFF, GRAD_RTOL, Case, grad_norm_err, grad_rel_err, make_case, oracle_run, upstream
+from helpers import DIFF, GRAD_RTOL, STRESS_CASES, Case, check_stress, grad_norm_err, grad_rel_err, make_case, \
+    oracle_run, upstream
 from oracle import raster as O
 
 pytestmark = pytest.mark.gpu
@@ -69,8 +70,14 @@ RASTER_CASES = {
     "2dgs": (lambda: make_case(n=300, n_texels=0, H=64, W=80, seed=1), None),
     "photometric": (lambda: make_case(n=300, n_texels=20000, H=64, W=80, seed=2), ("img", "alpha", "tex")),
     "intrinsics": (_intrinsics_case, None),
+    # helpers.STRESS_CASES: anisotropic splats, non-square charts, glob_scale 1.4; a camera at the edge of the splat
+    # cube, where the view-matrix gradient is largest relative to the depths it divides by
+    "aniso": (lambda: make_case(**STRESS_CASES["aniso10_glob"]), None),
+    "near": (lambda: make_case(**STRESS_CASES["near1.3"]), None),
 }
+STRESS = {"aniso": "aniso10_glob", "near": "near1.3"}
 _RASTER_REF: dict = {}
+_RASTER_FP32: dict = {}  # the oracle's own fp32-autograd error of each reference (the yardstick, not a bound)
 
 
 def _raster_ref(name):
@@ -81,12 +88,18 @@ def _raster_ref(name):
         inp, cam0 = case.inp, case.inp.cam
         V = cam0.viewmat.double().clone().requires_grad_(True)
         inp.cam = O.Camera(V, cam0.fx, cam0.fy, cam0.cx, cam0.cy, cam0.H, cam0.W, cam0.block, cam0.campos)
-        _, _, _, og = oracle_run(case, grads=True, outputs=outputs)  # (sets case.flip_mask)
+        _, _, aux, og = oracle_run(case, grads=True, outputs=outputs)  # (sets case.flip_mask)
+        if name in STRESS:
+            check_stress(STRESS[name], case, aux)
         g_raster = V.grad.detach().clone()
         V.grad = None
         c64, _ = O.aabb_2d(inp.means, inp.scales, inp.glob_scale, inp.quats, inp.cam, dtype=F64)
         (c64 * og["centers"].double()).sum().backward()
         g_centres = V.grad.detach().clone()
+        V.grad = None
+        oracle_run(case, grads=True, grad_dtype=torch.float32, outputs=outputs)
+        _RASTER_FP32[name] = (grad_norm_err(V.grad, g_raster), grad_rel_err(V.grad, g_raster)[0])
+        V.grad = None
         inp.cam = cam0
         _RASTER_REF[name] = (case, outputs, g_raster, g_centres)
     return _RASTER_REF[name]
@@ -121,6 +134,8 @@ def _gpu_raster(case, outputs, fold, pose, through_aabb=False):
 
 def _check_raster(name, det):
     case, outputs, g_raster, g_centres = _raster_ref(name)
+    print(f"[pose] {name} viewmat (raster part), the oracle's own fp32 autograd: norm err {_RASTER_FP32[name][0]:.3e}, "
+          f"max-element rel err {_RASTER_FP32[name][1]:.3e}")
     for fold in (False, True):
         base, base_names = _gpu_raster(case, outputs, fold, pose=False)
         got, names = _gpu_raster(case, outputs, fold, pose=True)

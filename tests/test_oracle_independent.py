@@ -7,7 +7,9 @@ through the pixel centre, its intersection with each splat's plane in the splat'
 c + u a + v b = lambda d, a = R t_u s_u, b = R t_v s_v in camera coordinates), rho3 = u^2 + v^2 against the screen-space
 low-pass rho2 = 2 |centre - pixel|^2 (AA bit 9), alpha = min(0.99, o exp(-rho / 2)) with the 1/255 and near-plane
 skips, front-to-back compositing in each tile's (depth, id) order with the T < 1e-4 termination, the hit point's
-view depth, the camera-facing world normal, and the texel lookup at uv0 + (umap, vmap) . (hit - mu) in texel units
+view depth, the camera-facing world normal, the 2DGS depth-distortion term reg = sum_i sum_{j<i} w_i w_j (m_i - m_j)^2
+over each pixel's contributors (m = far / (far - near) (1 - near / z), as a double sum over pairs of contributors, not
+the kernels' running sums), and the texel lookup at uv0 + (umap, vmap) . (hit - mu) in texel units
 (corner-aligned bilinear, clamped to the block).  The per-tile lists are the oracle's binning (itself checked against
 brute force in test_oracle.py).  Pixels whose oracle decisions lie within FLIP_MARGIN of a threshold are left out
 (the oracle takes fp32 decisions, this restatement fp64 ones)."""
@@ -15,10 +17,14 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import FLIP_MARGIN, make_case
+from helpers import DIFF, FLIP_MARGIN, STRESS_CASES, make_case, upstream
 from oracle import raster as O
 
 NEAR, AMAX, AMIN, TMIN = 0.2, 0.99, 1.0 / 255.0, 1e-4
+# the distortion term's constants as the kernels take them (fp32 values, like f32(fx) below)
+NEAR32 = float(np.float32(0.2))
+FAR_RATIO32 = float(np.float32(np.float32(100) / np.float32(99.8)))
+OUTPUTS = ("img", "alpha", "depth", "reg", "tex", "normal")
 
 
 def rotation(q):
@@ -54,11 +60,12 @@ def ray_render(inp):
     uv0 = inp.uv0[:, 0, :].double().numpy()
     um, vm = inp.umap[:, 0, :].double().numpy(), inp.vmap[:, 0, :].double().numpy()
     aa = bool(inp.settings & O.SETTING_AA_BLUR)
+    dreg = bool(inp.settings & O.SETTING_DIST_REG)
     C = tex.shape[1]
     _, tile_ranges, sorted_ids, _ = O.bin_and_sort(inp.centers, inp.extents, inp.depths, H, W)
     tiles_x = (W + 15) // 16
-    out = {k: np.zeros((H, W) + s) for k, s in (("img", (3,)), ("alpha", ()), ("depth", ()), ("tex", (C,)),
-                                                  ("normal", (3,)))}
+    out = {k: np.zeros((H, W) + s) for k, s in (("img", (3,)), ("alpha", ()), ("depth", ()), ("reg", ()),
+                                                  ("tex", (C,)), ("normal", (3,)))}
     for t, (s, e) in enumerate(tile_ranges):
         ids = sorted_ids[s:e]
         ty, tx = divmod(t, tiles_x)
@@ -67,6 +74,7 @@ def ray_render(inp):
                 d = np.array([(px + 0.5 - cx) / fx, (py + 0.5 - cy) / fy, 1.0])
                 T = 1.0
                 acc = {k: np.zeros_like(v[0, 0]) for k, v in out.items()}
+                ws, ms = [], []  # the pixel's contributors: blend weight and mapped depth
                 for g in ids:
                     M = np.stack([a[g], b[g], -d], 1)
                     if abs(np.linalg.det(M)) < 1e-300:
@@ -86,6 +94,8 @@ def ray_render(inp):
                     acc["img"] += w * rgb[g]
                     acc["depth"] += w * z
                     acc["normal"] += w * nrm[g]
+                    ws.append(w)
+                    ms.append(FAR_RATIO32 * (1.0 - NEAR32 / z))
                     h_, w_, off = dims[g]
                     if h_ * w_ > 0:
                         hit = mu[g] + u * su[g] * t_u[g] + v * sv[g] * t_v[g]
@@ -101,6 +111,8 @@ def ray_render(inp):
                         acc["tex"] += w * val
                     T *= 1.0 - alpha
                 acc["alpha"] = 1.0 - T
+                if dreg:
+                    acc["reg"] = sum(ws[i] * ws[j] * (ms[i] - ms[j]) ** 2 for i in range(len(ws)) for j in range(i))
                 for k in out:
                     out[k][py, px] = acc[k]
     return out
@@ -110,7 +122,7 @@ def ray_render(inp):
     ("aa_dist", dict(n=120, n_texels=6000, H=40, W=48, seed=3)),
     ("no_aa", dict(n=120, n_texels=6000, H=40, W=48, seed=4, settings=1 << 10)),
     ("2dgs", dict(n=150, n_texels=0, H=32, W=48, seed=5)),
-])
+] + list(STRESS_CASES.items()))
 def test_world_space_ray_restatement_matches_oracle(name, kw):
     case = make_case(**kw)
     o32, o64, aux = O.rasterize(case.inp)
@@ -118,7 +130,8 @@ def test_world_space_ray_restatement_matches_oracle(name, kw):
     ok = (aux["margin"] >= FLIP_MARGIN).numpy()
     assert ok.mean() > 0.95
     assert float(ref["alpha"][ok].max()) > 0.5, "the scene must cover the image"
-    for k in ("img", "alpha", "depth", "tex", "normal"):
+    assert float(ref["reg"][ok].max()) > 0
+    for k in OUTPUTS:
         a = o64[k].double().numpy()[ok]
         b = ref[k][ok]
         err = float(np.abs(a - b).max())
@@ -128,9 +141,10 @@ def test_world_space_ray_restatement_matches_oracle(name, kw):
 
 def ray_render_torch(inp, leaves):
     """The same world-space restatement in torch float64, differentiable w.r.t. the leaves (means, scales, quats,
-    opacities, rgbs, texture, centers): per tile, every (splat, pixel) pair's ray-plane system solved by Cramer's
+    opacities, rgbs, texture, centers, uv0): per tile, every (splat, pixel) pair's ray-plane system solved by Cramer's
     rule, the pair decisions (skips, low-pass branch, termination) taken in float64 without gradient, the composite
-    as a product scan.  Outputs img, alpha, depth, tex, normal of the whole image."""
+    as a product scan, the distortion term as the double sum over a pixel's pairs of contributors.  Outputs img, alpha,
+    depth, reg, tex, normal of the whole image."""
     cam = inp.cam
     H, W = cam.H, cam.W
     f32 = lambda v: float(np.float32(v))  # noqa: E731
@@ -159,13 +173,14 @@ def ray_render_torch(inp, leaves):
     ctr = leaves["centers"].to(F)
     tex = leaves["texture"].to(F)
     dims = inp.texture_dims.long()
-    uv0 = inp.uv0[:, 0, :].to(F)
+    uv0 = leaves["uv0"][:, 0, :].to(F)
     um, vm = inp.umap[:, 0, :].to(F), inp.vmap[:, 0, :].to(F)
     aa = bool(inp.settings & O.SETTING_AA_BLUR)
+    dreg = bool(inp.settings & O.SETTING_DIST_REG)
     C = tex.shape[1]
     _, tile_ranges, sorted_ids, _ = O.bin_and_sort(inp.centers, inp.extents, inp.depths, H, W)
     tiles_x = (W + 15) // 16
-    out = {k: torch.zeros((H, W) + s, dtype=F) for k, s in (("img", (3,)), ("alpha", ()), ("depth", ()),
+    out = {k: torch.zeros((H, W) + s, dtype=F) for k, s in (("img", (3,)), ("alpha", ()), ("depth", ()), ("reg", ()),
                                                               ("tex", (C,)), ("normal", (3,)))}
     rows = {k: [] for k in out}
     pix_all = []
@@ -223,7 +238,14 @@ def ray_render_torch(inp, leaves):
             val = torch.zeros(len(ids), len(xs), C, dtype=F)
         rows["img"].append((w[..., None] * rgb[ids][:, None, :]).sum(0))
         rows["alpha"].append(1.0 - torch.prod(1.0 - ai, 0))
-        rows["depth"].append((w * torch.where(incl, z, torch.ones_like(z))).sum(0))
+        zs = torch.where(incl, z, torch.ones_like(z))
+        rows["depth"].append((w * zs).sum(0))
+        if dreg:
+            m = FAR_RATIO32 * (1.0 - NEAR32 / zs)
+            earlier = torch.tril(torch.ones(len(ids), len(ids), dtype=F), -1)[:, :, None]  # [i, j] = (j < i)
+            rows["reg"].append((w[:, None, :] * w[None, :, :] * (m[:, None, :] - m[None, :, :]) ** 2 * earlier).sum((0, 1)))
+        else:
+            rows["reg"].append(torch.zeros(len(xs), dtype=F))
         rows["tex"].append((w[..., None] * val).sum(0))
         rows["normal"].append((w[..., None] * nrm[ids][:, None, :]).sum(0))
         pix_all.append(ys * W + xs)
@@ -234,35 +256,47 @@ def ray_render_torch(inp, leaves):
     return out
 
 
-@pytest.mark.parametrize("n_texels,keys", [
-    # 2DGS mode: every gradient
-    (0, ("rgbs", "opacities", "means", "scales", "quats", "centers")),
-    # textured: the oracle takes the texel cell of each pair from the fp32 pass (what the kernels see), this
-    # restatement from float64, so where a sample point lies within an fp32 ulp of a texel edge the two bilinear
-    # slopes differ -- the coordinate gradients (means, scales, quats) are compared on the 2DGS scene only
-    (3000, ("rgbs", "opacities", "texture", "centers")),
-])
-def test_world_space_ray_restatement_gradients_match_oracle(n_texels, keys):
-    """The oracle's fp64 autograd (of the kernels' formulation) against autograd of the world-space restatement, for
-    the same upstream gradients, both in float64: equal to 1e-10 of each gradient's largest element."""
-    from helpers import DIFF, upstream
+GRAD_CASES = {
+    "2dgs": dict(n=60, n_texels=0, H=32, W=32, seed=21),
+    "textured": dict(n=60, n_texels=3000, H=32, W=32, seed=21),
+    **{k: STRESS_CASES[k] for k in ("aniso10_glob", "near1.3", "inside0.5_aniso4", "2dgs_near")},
+}
 
-    case = make_case(n=60, n_texels=n_texels, H=32, W=32, seed=21)
+
+@pytest.mark.parametrize("name", list(GRAD_CASES))
+def test_world_space_ray_restatement_gradients_match_oracle(name):
+    """The oracle's fp64 autograd (of the kernels' formulation) against autograd of the world-space restatement, for
+    the same upstream gradients, both in float64: every gradient equal to 1e-10 of its largest element, with an
+    upstream over all six outputs and once more with one over reg alone."""
+    case = make_case(**GRAD_CASES[name])
     inp = case.inp
+    H, W = inp.cam.H, inp.cam.W
+    keys = [k for k in DIFF if k != "texture" or inp.texture.shape[0]]  # (2DGS mode has no texels)
     mine = {k: getattr(inp, k).detach().clone().double().requires_grad_(True) for k in DIFF}
     theirs = {k: getattr(inp, k).detach().clone().double().requires_grad_(True) for k in DIFF}
     for k, t in theirs.items():
         setattr(inp, k, t)
     _, o64, aux = O.rasterize(inp)
-    up = upstream(32, 32, case.C, 5, aux["margin"] < FLIP_MARGIN)
-    names = ("img", "alpha", "depth", "tex", "normal")
-    sum((o64[k] * up[k].double()).sum() for k in names).backward()
     ref = ray_render_torch(inp, mine)
-    sum((ref[k] * up[k].double()).sum() for k in names).backward()
-    for k in names:
+    up = upstream(H, W, case.C, 5, aux["margin"] < FLIP_MARGIN)
+    for k in OUTPUTS:
         assert float((ref[k] - o64[k]).detach().abs().max()) < 1e-10, k
-    for k in keys:
-        g, r = theirs[k].grad, mine[k].grad
-        scale = float(r.abs().max())
-        assert scale > 0, k
-        assert float((g - r).abs().max()) <= 1e-10 * scale, f"{k}: {float((g - r).abs().max()):.3e} vs {scale:.3e}"
+    for names in (OUTPUTS, ("reg",)):
+        for t in list(mine.values()) + list(theirs.values()):
+            t.grad = None
+        sum((o64[k] * up[k].double()).sum() for k in names).backward(retain_graph=True)
+        sum((ref[k] * up[k].double()).sum() for k in names).backward(retain_graph=True)
+        errs = {}
+        for k in keys:
+            g, r = theirs[k].grad, mine[k].grad
+            # reg does not depend on the colours; without texels nothing depends on uv0
+            if (names == ("reg",) and k in ("rgbs", "texture", "uv0")) or (k == "uv0" and not inp.texture.shape[0]):
+                assert (g is None or float(g.abs().max()) == 0.0) and (r is None or float(r.abs().max()) == 0.0), k
+                continue
+            scale = float(r.abs().max())
+            assert scale > 0, k
+            errs[k] = float((g - r).abs().max()) / scale
+        print(f"[restatement] {name} upstream {'+'.join(names) if len(names) == 1 else 'all six'}: "
+              + ", ".join(f"{k}={v:.1e}" for k, v in errs.items()))
+        for k, e in errs.items():
+            assert e <= 1e-10, f"{name} ({names}): {k} differs by {e:.3e} of its largest element"
