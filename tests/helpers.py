@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import dataclasses
 import math
+import re
 from dataclasses import dataclass
 
 import numpy as np
@@ -73,16 +74,27 @@ def make_case(n=300, n_texels=20000, H=64, W=80, seed=0, view=0, opacity=None, C
 DIFF = ["rgbs", "opacities", "means", "scales", "quats", "texture", "centers", "uv0"]
 
 
-def upstream(H, W, C, seed=5, mask=None):
-    """Seeded upstream gradients of the six outputs; zero at the pixels of `mask` (H, W bool) if given."""
+def upstream(H, W, C, seed=5, mask=None, tex_channel_scale=None):
+    """Seeded upstream gradients of the six outputs; zero at the pixels of `mask` (H, W bool) if given.
+    tex_channel_scale: C factors, one per channel of the tex upstream (the same draws, scaled)."""
     g = torch.Generator().manual_seed(seed)
     up = dict(img=torch.randn(H, W, 3, generator=g), depth=torch.randn(H, W, generator=g),
               reg=torch.randn(H, W, generator=g), alpha=torch.randn(H, W, generator=g),
               tex=torch.randn(H, W, C, generator=g), normal=torch.randn(H, W, 3, generator=g))
+    if tex_channel_scale is not None:
+        scale = torch.as_tensor(tex_channel_scale, dtype=torch.float32)
+        assert scale.shape == (C,)
+        up["tex"] = up["tex"] * scale
     if mask is not None and bool(mask.any()):
         for k, v in up.items():
             v[mask] = 0.0
     return up
+
+
+def _scale_kw(tex_channel_scale):
+    """upstream()'s per-channel scale as a keyword, passed only when one is given (a test may put an upstream of the
+    five-argument form in this module's place)."""
+    return {} if tex_channel_scale is None else {"tex_channel_scale": tex_channel_scale}
 
 
 def _differentiable(settings, outputs):
@@ -93,9 +105,10 @@ def _differentiable(settings, outputs):
     return outputs
 
 
-def oracle_run(case: Case, grads=True, seed=5, grad_dtype=torch.float64, outputs=None, flip_mask=None):
+def oracle_run(case: Case, grads=True, seed=5, grad_dtype=torch.float64, outputs=None, flip_mask=None,
+               tex_channel_scale=None):
     """flip_mask: use this mask (e.g. one computed on another machine, whose CPU exp may round differently) instead of
-    the one this run's margins give."""
+    the one this run's margins give.  tex_channel_scale: see upstream()."""
     inp = case.inp
     leaves = {}
     if grads:
@@ -110,7 +123,7 @@ def oracle_run(case: Case, grads=True, seed=5, grad_dtype=torch.float64, outputs
     out = {}
     outputs = _differentiable(inp.settings, outputs)
     if grads:
-        up = upstream(inp.cam.H, inp.cam.W, case.C, seed, case.flip_mask)
+        up = upstream(inp.cam.H, inp.cam.W, case.C, seed, case.flip_mask, **_scale_kw(tex_channel_scale))
         loss = sum((o64[k] * up[k].to(grad_dtype)).sum() for k in up if outputs is None or k in outputs)
         loss.backward()
         out = {k: (v.grad.detach().clone() if v.grad is not None else torch.zeros_like(v).detach()).float()
@@ -120,9 +133,9 @@ def oracle_run(case: Case, grads=True, seed=5, grad_dtype=torch.float64, outputs
     return o32, o64, aux, out
 
 
-def gpu_run(case: Case, grads=True, seed=5, device="cuda", outputs=None):
+def gpu_run(case: Case, grads=True, seed=5, device="cuda", outputs=None, tex_channel_scale=None):
     """outputs: names of the outputs that receive an upstream gradient (default all six; the others
-    reach the kernel as NULL, as for outputs the loss does not use)."""
+    reach the kernel as NULL, as for outputs the loss does not use).  tex_channel_scale: see upstream()."""
     import gstex_cuda
 
     inp = case.inp
@@ -143,7 +156,7 @@ def gpu_run(case: Case, grads=True, seed=5, device="cuda", outputs=None):
     gr = {}
     outputs = _differentiable(inp.settings, outputs)
     if grads:
-        up = upstream(inp.cam.H, inp.cam.W, case.C, seed, case.flip_mask)
+        up = upstream(inp.cam.H, inp.cam.W, case.C, seed, case.flip_mask, **_scale_kw(tex_channel_scale))
         sel = [i for i, k in enumerate(names) if outputs is None or k in outputs]
         torch.autograd.backward([outs[i] for i in sel], [up[names[i]].to(device) for i in sel])
         gr = {k: (t[k].grad.detach().cpu() if t[k].grad is not None else torch.zeros_like(t[k]).cpu()) for k in t}
@@ -208,6 +221,76 @@ def check_stress(name, case, aux):
     H, W = inp.cam.H, inp.cam.W
     near_flip = int((aux["margin"] < FLIP_MARGIN).sum())
     assert near_flip <= max(4, FLIP_FRACTION * H * W), f"{name}: {near_flip} pixels within FLIP_MARGIN of a threshold"
+
+
+# Channel counts without an instantiation of their own (every C but 3 and 6 runs the raster kernels' runtime-channel
+# build, raster.hip: CM = 8 register slots, Cn = the call's C), at C > 1 so that a wrong channel stride moves an address:
+# C = 8 (every slot live), a C = 8 case with texel blocks on both sides of the backward's staging size, an odd C on a
+# ragged image, C = 2, C = 4 without the AA branch, C = 7 with a background.  Fixed inputs; check_channels asserts, from
+# the oracle's run alone, that each reaches its regime.  Seeds tried: the ones below only.
+CHANNEL_CASES = {
+    "tex8": dict(n=200, n_texels=8000, H=40, W=40, seed=12, C=8),
+    "tex8_mixed_blocks": dict(n=80, n_texels=10000, H=40, W=40, seed=13, C=8),
+    "tex5_ragged": dict(n=150, n_texels=5000, H=17, W=33, seed=14, C=5),
+    "tex2": dict(n=200, n_texels=8000, H=40, W=40, seed=15, C=2),
+    "tex4_noaa": dict(n=200, n_texels=8000, H=40, W=40, seed=16, C=4, settings=1 << 10),
+    "tex7_bg": dict(n=200, n_texels=8000, H=40, W=40, seed=17, C=7, bg=(0.2, 0.5, 0.9)),
+}
+CHANNEL_PHOTOMETRIC = ("tex8", "tex8_mixed_blocks", "tex5_ragged", "tex2")
+# C = 5 for the deterministic per-pair rows against the float-atomic sums, and for bitwise reproducibility
+ROWS_CASES = {"rows_tex5": dict(n=300, n_texels=12000, H=48, W=48, seed=29, C=5)}
+# Tile lists of three kSegLen = 256 segments (multi-segment checkpoints, whose field count and plane offsets follow C)
+# at C = 8 and C = 5.  Seeds tried: C = 8: n=2500, seed=18 (8 pixels near a threshold, cap 4), then 19 (2 pixels);
+# C = 5: 20 (5 pixels), then 21 (2 pixels).
+DEEP_CHANNEL_CASES = {
+    "deep_tex8": dict(n=1500, n_texels=15000, H=32, W=32, seed=19, C=8, opacity=0.05),
+    "deep_tex5": dict(n=1500, n_texels=15000, H=32, W=32, seed=21, C=5, opacity=0.05),
+}
+TEX_STAGE = 1024  # the backward's texel staging size in entries (raster.hip: kTexStage, GSTEX_TEX_STAGE's default)
+SEG_LEN = 256  # tile-list positions per checkpoint segment (raster.hip: kSegLen, GSTEX_SEG_LEN's default)
+
+
+def check_channels(name, case, aux):
+    """The generic-channel case reaches the regime it is named for: facts of the oracle's run, not of the code under
+    test."""
+    inp = case.inp
+    C = int(re.search(r"tex(\d)", name).group(1))
+    assert case.C == C and inp.texture.shape[1] == C and C not in (1, 3, 6), f"{name}: C = {case.C}"
+    n = inp.means.shape[0]
+    seen = torch.zeros(n, dtype=torch.bool)  # splats on some tile list
+    seen[torch.as_tensor(aux["sorted_ids"]).long()] = True
+    entries = (inp.texture_dims[:, 0].long() * inp.texture_dims[:, 1].long() * C)[seen]
+    assert entries.numel() > 0 and int(entries.min()) > 0
+    # a block of h * w * C <= TEX_STAGE entries is summed in the staging area and flushed, a larger one goes
+    # straight to global atomics (raster_bwd_kernel: staged = bsize <= kTexStage)
+    staged, unstaged = int((entries <= TEX_STAGE).sum()), int((entries > TEX_STAGE).sum())
+    if name == "tex8_mixed_blocks":
+        assert staged >= 10 and unstaged >= 10, f"{name}: {staged} staged blocks, {unstaged} above the staging size"
+    else:
+        assert unstaged == 0, f"{name}: {unstaged} blocks above the staging size"
+    H, W = inp.cam.H, inp.cam.W
+    near_flip = int((aux["margin"] < FLIP_MARGIN).sum())
+    assert near_flip <= max(4, FLIP_FRACTION * H * W), f"{name}: {near_flip} pixels within FLIP_MARGIN of a threshold"
+    assert float(aux["T_final"].detach().min()) < 0.5, f"{name}: alpha.max() <= 0.5"
+    return dict(staged=staged, unstaged=unstaged, largest=int(entries.max()) // C, near_flip=near_flip)
+
+
+def check_deep_channels(name, case, aux):
+    """The deep generic-channel case has three-segment tile lists with a contributor in the third segment (so the
+    backward restarts from two checkpoints and reads the final accumulators from the third slot): oracle facts."""
+    inp = case.inp
+    C = int(re.search(r"tex(\d)", name).group(1))
+    assert case.C == C and inp.texture.shape[1] == C and C not in (1, 3, 6), f"{name}: C = {case.C}"
+    tr = np.asarray(aux["tile_ranges"])
+    lens = tr[:, 1] - tr[:, 0]
+    assert int(lens.min()) > 2 * SEG_LEN, f"{name}: a tile list of {int(lens.min())}"
+    last = np.asarray(aux["last"])
+    assert int(last.max()) > 2 * SEG_LEN, f"{name}: deepest contributor at {int(last.max())}"
+    H, W = inp.cam.H, inp.cam.W
+    near_flip = int((aux["margin"] < FLIP_MARGIN).sum())
+    assert near_flip <= max(4, FLIP_FRACTION * H * W), f"{name}: {near_flip} pixels within FLIP_MARGIN of a threshold"
+    assert float(aux["T_final"].detach().min()) < 0.5, f"{name}: alpha.max() <= 0.5"
+    return dict(lists=(int(lens.min()), int(lens.max())), last=int(last.max()), near_flip=near_flip)
 
 
 def assert_close_fwd(gpu, ref64, names=("img", "depth", "reg", "alpha", "tex", "normal"), margin=None):

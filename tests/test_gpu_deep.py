@@ -8,21 +8,27 @@ tolerances of test_gpu_parity.py, on windows of the bench scenes themselves.
 * cfg1 exactly (1k splats, 0 texels = 2DGS mode, 256x256): the whole image;
 * cfg5's per-GPU raster (DTU-like stand-in: 200k splats, 1e7 texels, 1600x1200; the COLMAP init is absent): a
   48x48 window at the image centre with every output (depth, distortion, normal) and their gradients (the GEO
-  backward), ~2,500 splats per tile.
+  backward), ~2,500 splats per tile;
+* helpers.DEEP_CHANNEL_CASES: 1,500 splats of opacity 0.05 on a 32x32 image at C = 8 and C = 5 (the runtime-channel
+  build), ~680 splats per tile = three 256-segments with contributors in the third: the multi-segment checkpoints,
+  whose field count and plane offsets follow the channel count, with all outputs and photometric.
 """
 import numpy as np
 import pytest
 import torch
 
-from helpers import DIFF, assert_close_fwd, gpu_run, grad_norm_err, grad_rel_err, make_case, make_window_case, \
-    oracle_run
+from helpers import DEEP_CHANNEL_CASES, DIFF, SEG_LEN, assert_close_fwd, check_deep_channels, gpu_run, \
+    grad_norm_err, grad_rel_err, make_case, make_window_case, oracle_run
 from test_gpu_parity import GRAD_RTOL, _report
 
 pytestmark = pytest.mark.gpu
 
 
-def _check(name, case, outputs=None, min_depth=0):
+def _check(name, case, outputs=None, min_depth=0, regime=None):
+    """regime: a check of the oracle's run (name, case, aux) made before the GPU one."""
     o32, o64, aux, og = oracle_run(case, grads=True, outputs=outputs)
+    if regime is not None:
+        regime(name, case, aux)
     tr = np.asarray(aux["tile_ranges"])
     depth = int((tr[:, 1] - tr[:, 0]).max()) if tr.size else 0
     print(f"[deep] {name}: {case.inp.means.shape[0]} splats, {case.inp.texture.shape[0]} texels, "
@@ -78,3 +84,14 @@ def test_cfg1_exact():
     case = make_case(n=1000, n_texels=0, H=256, W=256, seed=42, opacity=0.1)
     assert case.inp.texture.shape[0] == 0 and int(case.inp.texture_dims.abs().sum()) == 0
     _check("cfg1 256x256", case)
+
+
+@pytest.mark.parametrize("outputs", [None, ("img", "alpha", "tex")], ids=["all", "photometric"])
+@pytest.mark.parametrize("name", list(DEEP_CHANNEL_CASES))
+def test_deep_tiles_generic_channels(name, outputs):
+    """Three-segment tile lists at C = 8 / C = 5: the forward's checkpoints (ck_fields(C) planes, the geometry planes
+    behind the C texture planes) and the backward's per-segment restart from them (the fin - ck differences over C
+    planes), with geometry gradients and without."""
+    case = make_case(**DEEP_CHANNEL_CASES[name])
+    tr, last = _check(name, case, outputs=outputs, min_depth=2 * SEG_LEN + 1, regime=check_deep_channels)
+    assert int(last.max()) > 2 * SEG_LEN, "a contributor in the third segment"

@@ -16,13 +16,23 @@ the oracle's fp64 autograd of the same function:
     max-element (aniso4 means, where the oracle's own fp32 autograd reads 2.33e-6), the forward within 2.1e-6 (depth),
     no flipped pixel; against the world-space restatement directly (aniso10_glob) <= 8.7e-7 / 1.02e-6.  No case takes
     an allowance over GRAD_RTOL.
+    The runtime-channel build (helpers.CHANNEL_CASES at C = 2, 4, 5, 7, 8, all outputs and photometric, and
+    helpers.DEEP_CHANNEL_CASES, three-segment tile lists at C = 8 / 5, in test_gpu_deep.py): the forward within 2.25e-6
+    (tex8 depth; tex within 9.8e-7, tex7_bg); every gradient <= 2.14e-6 norm-wise and <= 2.31e-6 max-element (both
+    tex8_mixed_blocks quats, where the oracle's own fp32 autograd reads 1.97e-6 / 2.19e-6); the texel gradient <=
+    9.05e-7 / 1.34e-6 (tex8_mixed_blocks, blocks on both sides of the staging size; fp32 oracle 8.57e-7 / 8.15e-7); no
+    flipped and no unexplained pixel in any case.  tex8 with the last channel's upstream gradient x 1024
+    (test_texel_fixed_point_bound_sees_the_last_channel): the texel gradient 7.8e-7 norm-wise / 1.0e-6 max-element
+    over the tensor; per channel 7.8e-7 for the large one and 3.0e-5 .. 3.5e-5 for the seven small ones (printed, not
+    bounded: the staging resolves 2^-30 of a visit's largest-channel total).
 """
 import numpy as np
 import pytest
 import torch
 
-from helpers import DIFF, FLIP_MARGIN, GRAD_RTOL, STRESS_CASES, assert_close_fwd, check_stress, cull_classes, \
-    gpu_run, grad_norm_err, grad_rel_err, make_case, oracle_run, upstream
+from helpers import CHANNEL_CASES, CHANNEL_PHOTOMETRIC, DIFF, FLIP_MARGIN, GRAD_RTOL, ROWS_CASES, STRESS_CASES, \
+    assert_close_fwd, check_channels, check_stress, cull_classes, gpu_run, grad_norm_err, grad_rel_err, make_case, \
+    oracle_run, upstream
 from oracle import raster as O
 
 pytestmark = pytest.mark.gpu
@@ -214,6 +224,8 @@ CASES = {
     "ragged_17x33": dict(n=150, n_texels=5000, H=17, W=33, seed=9),
     # ~1000 texels per splat: 16-splat batches overflow the LDS staging -> global-atomic texel path
     "big_texel_blocks": dict(n=60, n_texels=60000, H=64, W=64, seed=10),
+    # the runtime-channel build at C = 2, 4, 5, 7, 8 (helpers.CHANNEL_CASES; check_channels asserts their regimes)
+    **CHANNEL_CASES,
 }
 
 
@@ -224,7 +236,8 @@ def test_raster_forward_backward(name):
 
 # img / alpha / tex gradients only (depth, distortion and normal gradients None, the training default):
 # the backward runs its specialisation without those terms
-@pytest.mark.parametrize("name", ["tex3_default", "tex6_eval", "no_aa", "ragged_17x33", "big_texel_blocks"])
+@pytest.mark.parametrize("name", ["tex3_default", "tex6_eval", "no_aa", "ragged_17x33", "big_texel_blocks",
+                                  *CHANNEL_PHOTOMETRIC])
 def test_raster_backward_photometric_only(name):
     _check_raster(name, ("img", "alpha", "tex"))
 
@@ -247,6 +260,8 @@ def _check_raster(name, outputs):
     o32, o64, aux, og = oracle_run(case, grads=True, outputs=outputs)
     if name in STRESS_CASES:
         check_stress(name, case, aux)
+    if name in CHANNEL_CASES:
+        check_channels(name, case, aux)
     gout, gg = gpu_run(case, grads=True, outputs=outputs)
     fwd = {k: (gout[k].double() - o64[k]).abs().max().item() for k in gout}
     _report(f"{name} fwd", fwd)
@@ -261,6 +276,7 @@ def _check_raster(name, outputs):
     _report(f"{name} bwd max-rel", errs)
     _report(f"{name} bwd fp32-oracle max-rel", inherent)
     _report(f"{name} bwd norm-rel", norm_errs)
+    _report(f"{name} bwd fp32-oracle norm-rel", inherent_n)
     for k in DIFF:
         assert norm_errs[k] <= GRAD_RTOL, f"{name}: grad {k} norm-wise rel err {norm_errs[k]:.3e} > {GRAD_RTOL:.0e}"
         assert errs[k] <= GRAD_RTOL, f"{name}: grad {k} max rel err {errs[k]:.3e} > {GRAD_RTOL:.0e}"
@@ -326,7 +342,22 @@ def test_empty_and_offscreen():
 
 
 def test_backward_is_deterministic(deterministic):
-    case = make_case(n=300, n_texels=20000, H=64, W=64, seed=11)
+    _check_deterministic(make_case(n=300, n_texels=20000, H=64, W=64, seed=11))
+
+
+def test_backward_is_deterministic_tex5(deterministic):
+    # the per-pair rows behind the runtime-channel backward (C = 5)
+    _check_deterministic(_rows_case("rows_tex5"))
+
+
+def _rows_case(name):
+    """A case of helpers.ROWS_CASES, its regime asserted from the oracle's run (check_channels)."""
+    case = make_case(**ROWS_CASES[name])
+    check_channels(name, case, O.rasterize(case.inp)[2])
+    return case
+
+
+def _check_deterministic(case):
     _, g1 = gpu_run(case, grads=True)
     _, g2 = gpu_run(case, grads=True)
     for k in ["rgbs", "opacities", "means", "scales", "quats", "centers"]:
@@ -337,7 +368,16 @@ def test_backward_is_deterministic(deterministic):
 def test_atomic_splat_sums_match_rows(geo):
     """Default mode (per-splat float-atomic accumulators, no rows, no summing pass) against the deterministic
     per-pair rows: the same sums up to summation order, for 24-value (photometric) and 32-value rows."""
-    case = make_case(n=700, n_texels=30000, H=80, W=96, seed=29)
+    _check_atomic_sums_match_rows(make_case(n=700, n_texels=30000, H=80, W=96, seed=29), geo)
+
+
+@pytest.mark.parametrize("geo", [False, True])
+def test_atomic_splat_sums_match_rows_tex5(geo):
+    """The same at C = 5: the runtime-channel backward, photometric and with geometry gradients, in both modes."""
+    _check_atomic_sums_match_rows(_rows_case("rows_tex5"), geo)
+
+
+def _check_atomic_sums_match_rows(case, geo):
     outs = None if geo else ("img", "alpha", "tex")
     torch.use_deterministic_algorithms(True, warn_only=True)
     try:
@@ -348,7 +388,6 @@ def test_atomic_splat_sums_match_rows(geo):
     for k in ["rgbs", "opacities", "means", "scales", "quats", "centers", "uv0", "texture"]:
         assert grad_norm_err(g_atom[k], g_rows[k]) < 1e-6, k
         assert float(g_rows[k].abs().max()) > 0, k
-
 
 
 # ---------------------------------------------------------------- launch order (scheduling only)
@@ -621,9 +660,19 @@ def _check_texture_edit(case, seed):
 
 # ---------------------------------------------------------------- texel affine (SH2RGB on read)
 def test_texture_transform_equals_materialised_sh2rgb():
+    _check_texture_transform(3)
+
+
+def test_texture_transform_equals_materialised_sh2rgb_tex4():
+    # tex_scale / tex_bias in the runtime-channel forward (per-visit affine) and backward (Gtex_bias over 4 channels)
+    _check_texture_transform(4)
+
+
+def _check_texture_transform(C):
     from gstex_amd import ops
 
-    case = make_case(n=400, n_texels=30000, H=64, W=80, seed=17)
+    case = make_case(n=400, n_texels=30000, H=64, W=80, seed=17, C=C)
+    assert case.C == C and case.inp.texture.shape[1] == C
     inp, v = case.inp, case.view
     C0 = 0.28209479177387814
     g = torch.Generator().manual_seed(3)
@@ -632,13 +681,14 @@ def test_texture_transform_equals_materialised_sh2rgb():
     n = inp.means.shape[0]
 
     def run(tex_leaf, transform):
-        args = ((n, 1, 3), dv(inp.texture_dims), dv(inp.centers), dv(inp.extents), dv(inp.depths), dv(case.nth),
+        args = ((n, 1, case.C), dv(inp.texture_dims), dv(inp.centers), dv(inp.extents), dv(inp.depths), dv(case.nth),
                 dv(inp.rgbs), dv(inp.opacities), dv(inp.means), dv(inp.scales), 1.0, dv(inp.quats), dv(inp.uv0),
                 dv(inp.umap), dv(inp.vmap))
         outs = ops.texture_gaussians(*args, tex_leaf, dv(v.viewmat), dv(v.c2w), v.fx, v.fy, v.cx, v.cy,
                                      inp.cam.H, inp.cam.W, 16, inp.settings, texture_transform=transform)
-        up = upstream(inp.cam.H, inp.cam.W, 3, 5)
+        up = upstream(inp.cam.H, inp.cam.W, case.C, 5)
         names = ["img", "depth", "reg", "alpha", "tex", "normal"]
+        assert outs[4].shape == (inp.cam.H, inp.cam.W, case.C)
         torch.autograd.backward(list(outs), [up[k].to(DEV) for k in names])
         return [o.detach().cpu() for o in outs]
 
@@ -683,6 +733,30 @@ def test_texel_fixed_point_scale_invariance(gscale):
     a, b = gs["texture"].double() / gscale, gu["texture"].double()
     assert float(b.abs().max()) > 0
     assert float((a - b).norm() / b.norm()) < 4e-6
+
+
+def test_texel_fixed_point_bound_sees_the_last_channel():
+    """tex8 with an upstream gradient of tex alone whose last channel is 1024 times the others: the staging's
+    fixed-point bound is max_c |dL/dtex[c]| over the 8 register slots, and one that missed channel 7 would overflow
+    the int32 sums here.  The texture gradient holds GRAD_RTOL norm-wise and max-element over the whole tensor against
+    the oracle's fp64 autograd.  The per-channel errors are printed, not bounded: the staging resolves 2^-30 of a
+    visit's largest-channel total by design, so the small channels' relative error is a property of that design."""
+    name = "tex8"
+    case = make_case(**CASES[name])
+    C = case.C
+    scale = [1.0] * (C - 1) + [1024.0]
+    _, _, aux, og = oracle_run(case, grads=True, outputs=("tex",), tex_channel_scale=scale)
+    check_channels(name, case, aux)
+    _, gg = gpu_run(case, grads=True, outputs=("tex",), tex_channel_scale=scale)
+    g, ref = gg["texture"], og["texture"]
+    chan = ref.double().norm(dim=0)
+    assert float(chan[C - 1]) > 100 * float(chan[:C - 1].max()) and float(chan[:C - 1].min()) > 0
+    _report(f"{name} last channel x1024, texture norm-rel per channel",
+            {f"c{c}": grad_norm_err(g[:, c], ref[:, c]) for c in range(C)})
+    norm_err, max_err = grad_norm_err(g, ref), grad_rel_err(g, ref)[0]
+    _report(f"{name} last channel x1024, texture", {"norm-rel": norm_err, "max-rel": max_err})
+    assert norm_err <= GRAD_RTOL, f"texture norm-wise rel err {norm_err:.3e} > {GRAD_RTOL:.0e}"
+    assert max_err <= GRAD_RTOL, f"texture max rel err {max_err:.3e} > {GRAD_RTOL:.0e}"
 
 
 # ---------------------------------------------------------------- fused activations / SH without the DC cat
@@ -765,7 +839,17 @@ def test_fold_aabb_gradients_bit_identical(deterministic):
 def test_geometry_outputs_off_matches(deterministic):
     """geometry_outputs=False (photometric training path): img / alpha / tex and every gradient of a
     photometric upstream are bit-identical to the full render; depth / reg / normal come back as zeros."""
-    case = make_case(n=500, n_texels=25000, H=64, W=80, seed=23)
+    _check_geometry_outputs_off(make_case(n=500, n_texels=25000, H=64, W=80, seed=23))
+
+
+def test_geometry_outputs_off_matches_tex5(deterministic):
+    """The same at C = 5: the runtime-channel forward without geometry outputs against the one with them."""
+    case = make_case(n=500, n_texels=25000, H=64, W=80, seed=23, C=5)
+    assert case.C == 5 and case.inp.texture.shape[1] == 5
+    _check_geometry_outputs_off(case)
+
+
+def _check_geometry_outputs_off(case):
     import gstex_cuda
 
     v, inp = case.view, case.inp

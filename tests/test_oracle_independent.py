@@ -17,7 +17,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import DIFF, FLIP_MARGIN, STRESS_CASES, make_case, upstream
+from helpers import CHANNEL_CASES, DEEP_CHANNEL_CASES, DIFF, FLIP_MARGIN, ROWS_CASES, STRESS_CASES, check_channels, \
+    check_deep_channels, make_case, upstream
 from oracle import raster as O
 
 NEAR, AMAX, AMIN, TMIN = 0.2, 0.99, 1.0 / 255.0, 1e-4
@@ -122,7 +123,9 @@ def ray_render(inp):
     ("aa_dist", dict(n=120, n_texels=6000, H=40, W=48, seed=3)),
     ("no_aa", dict(n=120, n_texels=6000, H=40, W=48, seed=4, settings=1 << 10)),
     ("2dgs", dict(n=150, n_texels=0, H=32, W=48, seed=5)),
-] + list(STRESS_CASES.items()))
+] + list(STRESS_CASES.items()) + [
+    ("tex5", dict(n=120, n_texels=6000, H=40, W=48, seed=6, C=5)),  # (last: the ids above keep their kwN suffix)
+])
 def test_world_space_ray_restatement_matches_oracle(name, kw):
     case = make_case(**kw)
     o32, o64, aux = O.rasterize(case.inp)
@@ -259,6 +262,7 @@ def ray_render_torch(inp, leaves):
 GRAD_CASES = {
     "2dgs": dict(n=60, n_texels=0, H=32, W=32, seed=21),
     "textured": dict(n=60, n_texels=3000, H=32, W=32, seed=21),
+    "textured_c5": dict(n=60, n_texels=3000, H=32, W=32, seed=22, C=5),
     **{k: STRESS_CASES[k] for k in ("aniso10_glob", "near1.3", "inside0.5_aniso4", "2dgs_near")},
 }
 
@@ -300,3 +304,17 @@ def test_world_space_ray_restatement_gradients_match_oracle(name):
               + ", ".join(f"{k}={v:.1e}" for k, v in errs.items()))
         for k, e in errs.items():
             assert e <= 1e-10, f"{name} ({names}): {k} differs by {e:.3e} of its largest element"
+
+
+@pytest.mark.parametrize("name", list(CHANNEL_CASES) + list(ROWS_CASES) + list(DEEP_CHANNEL_CASES))
+def test_generic_channel_cases_reach_their_regimes(name):
+    """The generic-channel cases of the GPU parity tests (helpers.CHANNEL_CASES, ROWS_CASES, DEEP_CHANNEL_CASES), by
+    the oracle alone: the channel count, texel blocks on the named side(s) of the backward's staging size, tile lists
+    and contributors in the third segment, few pixels near a threshold, an opaque pixel."""
+    if name in DEEP_CHANNEL_CASES:
+        case = make_case(**DEEP_CHANNEL_CASES[name])
+        facts = check_deep_channels(name, case, O.rasterize(case.inp)[2])
+    else:
+        case = make_case(**{**CHANNEL_CASES, **ROWS_CASES}[name])
+        facts = check_channels(name, case, O.rasterize(case.inp)[2])
+    print(f"[regime] {name}: {facts}")
