@@ -27,7 +27,7 @@ class GradSync:
     all-reduce as soon as its gradient is final, overlapping the collective with the rest of the backward
     (setup_bwd, SH, activations); all_reduce() then reduces the head of the buffer and waits for both.
 
-    A trainer that exposes ``texture_grad_sink`` / ``texture_grad_ready`` (gstex_amd.model.GStexTrainer) gets
+    A trainer with a ``texel_grad`` (gstex_amd.texel_grad.TexelGrad; gstex_amd.model.GStexTrainer) is handed
     the tail slice of the flat buffer as the raster backward's texel-gradient target: the kernel accumulates
     straight into the buffer (no separate zero-filled gradient tensor, no autograd accumulation pass) and the
     tail collective starts right after that kernel is enqueued.  Other parameter holders use a
@@ -39,7 +39,7 @@ class GradSync:
     is not supported (the tail would be reduced after the first).
 
     Several differentiable renders per step (gradient accumulation over views) with the tail started early: the
-    trainer asks texture_grad_route(first) for each render's texel-gradient target; once the tail's collective is on
+    trainer's TexelGrad asks _route(first) for each render's texel-gradient target; once the tail's collective is on
     the wire, later renders of the step accumulate into a side buffer instead, which the step reduces and adds to the
     slice after the tail has landed."""
 
@@ -57,9 +57,10 @@ class GradSync:
         self._hook = None
         self._hooked = None
         self._work = None
-        self._extra = None  # the side buffer of renders after the tail's early start (texture_grad_route)
+        self._extra = None  # the side buffer of renders after the tail's early start (_route)
         self._extra_live = False
-        self._sink = hasattr(trainer, "texture_grad_sink")
+        # the raster zeroes and accumulates into the tail slice itself (else: autograd and a hook on the tail)
+        self._sink = hasattr(trainer, "texel_grad")
         # head first (a trainer that defers its texel update into the next step, GStexTrainer defer_texture): the
         # tail's collective is not started from the raster backward but queued right behind the head's at the step,
         # so the head (45 MB) lands first, the next step starts on it, and the tail (120 MB) only has to land by that
@@ -111,15 +112,8 @@ class GradSync:
         self._key = key
         self._tail_off = offs[-1]
         if self._sink:
-            self.trainer.texture_grad_sink = params[-1].grad
-            self.trainer.texture_grad_ready = (self._tail_ready_sink if self.overlap_tail and not self.head_first
-                                               else None)
-            self.trainer.texture_grad_route = self._route
-            # the trainer's second (double-buffered) texel-gradient buffer is never used once the flat buffer's slice
-            # is the sink (GStexTrainer._double_buffered() is False): free it
-            if getattr(self.trainer, "_tex_grad_next", None) is not None:
-                self.trainer._tex_grad_next = None
-                self.trainer._next_zeroed = False
+            self._ready = self._tail_ready_sink if self.overlap_tail and not self.head_first else None
+            self.trainer.texel_grad.attach(params[-1].grad, self._ready, self._route)
         else:
             self._install_hook(params[-1])
         return True
@@ -149,9 +143,9 @@ class GradSync:
         """(target, zero, ready) of one render's texel gradient: the flat buffer's slice (zeroed by that render when
         `first`, the tail collective started once its backward is enqueued), or -- when an earlier render of the step
         already started the tail's collective -- the side buffer, reduced and added by the step."""
-        tail = self.trainer.texture_grad_sink
+        tail = self.trainer.texel_grad.sink
         if self._work is None:
-            return tail, first, self.trainer.texture_grad_ready
+            return tail, first, self._ready
         if self._extra is None or self._extra.shape != tail.shape:
             self._extra = torch.zeros_like(tail)
             self._extra_live = True
@@ -179,17 +173,13 @@ class GradSync:
     def zero(self):
         if self._work is not None:
             raise RuntimeError("GradSync.zero(): the previous backward's all_reduce() was never called")
-        reset = getattr(self.trainer, "reset_texture_grad", None)
-        if reset is not None:
-            reset()  # the sink (the texel slice) is zeroed by the next differentiable raster forward
-        if self.rebuild():
-            return  # a new buffer is zero
-        if getattr(self.trainer, "texture_grad_zeroed_by_update", False):
+        if self._sink:
             # the texel slice is zeroed by the next differentiable raster forward (gstex_raster_fwd zero_buf); filling it
             # here would pre-empt the deferred texel update (defer_texture) still reading it
-            self.flat[self._z0:self._tail_off].zero_()
-        else:
-            self.flat[self._z0:].zero_()
+            self.trainer.texel_grad.reset()
+        if self.rebuild():
+            return  # a new buffer is zero
+        self.flat[self._z0:self._tail_off if self._sink else None].zero_()
 
     def all_reduce(self):
         """Average the flat gradient buffer over all ranks (the tail's collective may already be running).

@@ -83,8 +83,8 @@ def _view(arena: torch.Tensor, off: int, shape) -> torch.Tensor:
 
 class _TrainRender(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, tr, view, degree, sink, zero_sink, first, on_grad, texture_ready, zero_next, means, quats,
-                log_scales, opac_logits, features_rest):
+    def forward(ctx, tr, view, degree, target, texture_ready, means, quats, log_scales, opac_logits, features_rest):
+        sink, zero_sink, first, on_grad, zero_next = target  # (TexelGrad.target)
         n = means.shape[0]
         n_rest = features_rest.shape[1]
         H, W, C = int(view.H), int(view.W), 3
@@ -92,9 +92,7 @@ class _TrainRender(torch.autograd.Function):
         st = _lib.stream_of(dev)
         pcap = tr.pairs
         step_flag = tr._skip_flag()
-        # `first`: the step's first render, which resets the step's guard flag (not whether the sink is zeroed here:
-        # with the double-buffered texel gradient the previous backward zeroed it)
-        guard, slot, cap = pcap.reserve(step_flag, bool(first), tr.step)
+        guard, slot, cap = pcap.reserve(step_flag, first, tr.step)  # (the step's first render resets its guard flag)
         off, nbytes, sizes, goff, gfloats = _layout(n, n_rest, cap, H, W, C)
         arena = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
         base = arena.data_ptr()
@@ -157,10 +155,9 @@ class _TrainRender(torch.autograd.Function):
             scene=scene, sorted_slots=P["sorted_slots"], v_img=ptr(v_img), v_alpha=ptr(v_alpha), v_tex=ptr(v_tex),
             partials=P["partials"], v_texture=ptr(ctx.sink))
         zn = ctx.zero_next
-        if zn is not None and zn is tr._tex_grad_next and zn.data_ptr() != ctx.sink.data_ptr():
+        if zn is not None and tr.texel_grad.zeroed_by_backward(zn, ctx.sink):
             # the trainer's other texel-gradient buffer, zeroed by this backward's grid for the next step
             bwd.zero_buf, bwd.zero_floats = ptr(zn), zn.numel()
-            tr._next_zeroed = True
         ops._launch("gstex_raster_bwd", ctypes.byref(bwd), st)
         ctx.zero_next = None
         if ctx.on_grad is not None:
@@ -184,7 +181,7 @@ class _TrainRender(torch.autograd.Function):
 
         def gv(name, shape):
             return _view_f(grads, o[name], shape)
-        return (None, None, None, None, None, None, None, None, None, gv("means", (n, 3)), gv("quats", (n, 4)), gv("log_scales", (n, 3)),
+        return (None, None, None, None, None, gv("means", (n, 3)), gv("quats", (n, 4)), gv("log_scales", (n, 3)),
                 gv("opac_logits", (n, 1)), gv("features_rest", (n, n_rest, 3)))
 
 
@@ -195,12 +192,9 @@ def _view_f(flat: torch.Tensor, off: int, shape) -> torch.Tensor:
     return flat[off:off + nf].view(shape)
 
 
-def train_render(tr, view, degree: int, sink: torch.Tensor, zero_sink: bool, first: bool, on_grad=None,
-                 texture_ready=None, zero_next=None):
-    """-> (img (H,W,3), alpha (H,W), tex (H,W,3)) of GStexTrainer.render's photometric training branch; the texel
-    gradient accumulates into `sink` (zeroed by the raster forward when zero_sink), `first` marks the step's first
-    render (it resets the step's pair-capacity guard flag), and on_grad() runs once the raster
-    backward is enqueued; texture_ready() (a deferred texel update) runs right before the raster forward; zero_next
-    (the trainer's other texel-gradient buffer) is zeroed by the raster backward's grid."""
-    return _TrainRender.apply(tr, view, degree, sink, zero_sink, first, on_grad, texture_ready, zero_next, tr.means,
-                              tr.quats, tr.scales, tr.opacities, tr.features_rest)
+def train_render(tr, view, degree: int, target, texture_ready=None):
+    """-> (img (H,W,3), alpha (H,W), tex (H,W,3)) of GStexTrainer.render's photometric training branch.  target:
+    TexelGrad.target(fused=True)'s (sink, zero_sink, first, on_grad, zero_next) -- where the texel gradient accumulates
+    and which grid zeroes what; texture_ready() (a deferred texel update) runs right before the raster forward."""
+    return _TrainRender.apply(tr, view, degree, target, texture_ready, tr.means, tr.quats, tr.scales, tr.opacities,
+                              tr.features_rest)

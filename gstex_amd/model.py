@@ -32,6 +32,7 @@ from .loss import (ImageMetrics, depth_to_normal, gaussian_window, geometry_loss
 from .optim import FusedAdam
 from .charts import RGB2SH, SH2RGB, SH_C0, build_charts, get_uv_mapping, texture_dims_to_query
 from .scene import Scene, View
+from .texel_grad import TexelGrad
 
 # gstex-blender-nvs optimizer settings (gstex_configs.py:207-244)
 LRS = {
@@ -184,30 +185,18 @@ class GStexTrainer:
         self.lambda_normal = lambda_normal
         self.lambda_reg = lambda_reg
         self.use_normal_loss = use_normal_loss
-        # set by gstex_amd.dist.GradSync: the flat-buffer slice the raster backward accumulates the texel gradient
-        # into, and the callback that starts its collective (None: autograd owns the texel gradient)
-        self.texture_grad_sink = None
-        self.texture_grad_ready = None
-        self.texture_grad_route = None  # GradSync: the per-render texel-gradient target (several renders per step)
         self.test_colors = None  # eval-render test colours (gstex.py:309)
         # paint(): the (n_texels, 5) stroke accumulator (zero between calls: the blend kernel re-zeroes what the
         # scatter touched) and the per-splat scratch of its depth render
         self._paint_acc = None
         self._paint_scratch = {}
         # defer_texture (not in the reference; fused Adam on a HIP device): the texel parameter's Adam update of step k
-        # (73 % of the parameters at cfg3) runs at step k+1's zero_grad() or render, before the raster forward, the first reader of
-        # the texels -- at the pair-count read-back when there is one (the device runs it while the host waits), else
-        # right before the raster forward.  Same updates in the same order on the same stream; the gradient is a
-        # persistent buffer the raster forward zeroes (no per-step fill).  Readers of texture_dc outside the step go
-        # through wait_texture() / texels(), which run a pending update.  (A side-stream texel update, overlapping
-        # the next step's preprocessing and binning, measured no gain in rounds 2-3: the compute stream's kernels
-        # slow down under the streaming update by what the overlap saves; removed in round 5.)
+        # (73 % of the parameters at cfg3) runs in step k+1, before the raster forward, from a persistent gradient
+        # buffer the raster grids zero (DESIGN.md "The texel gradient's life cycle"; the slots: _pending_slots).
+        # Readers of texture_dc outside the step go through wait_texture() / texels(), which run a pending update.
         self.defer_texture = bool(defer_texture) and fused_adam and self.device.type == "cuda"
         self._pending_tex = None
         self._pending_collective = False  # the pending update first waits for a GradSync collective
-        # the texel-gradient sink is zeroed by the first differentiable raster forward after an optimizer step
-        # (gstex_raster_fwd zero_buf), so several renders of one step still accumulate their texel gradients
-        self._sink_fresh = True
         # pair_capacity (not in the reference; fused Adam on a HIP device): the training renders size their pair
         # buffers from an ops.PairCapacity instead of reading the pair total back to the host (gstex.py:1045-1052,
         # 1127), so a step has no host synchronisation.  Each step's renders write an overflow flag into
@@ -231,52 +220,29 @@ class GStexTrainer:
         if shared_grad is None:
             shared_grad = os.environ.get("GSTEX_SHARED_GRAD", "1") != "0"
         self.shared_grad = bool(shared_grad)
-        self._tex_grad = None
-        self._tex_grad_next = None
-        self._cur_zeroed = self._next_zeroed = False
+        self.texel_grad = TexelGrad()  # its buffers, zero flags and routing (as above)
         if self.defer_texture:
-            self._own_texture_grad()
+            self.texel_grad.own(self.texture_dc, self.fused_step)
         self._build_optimizer()
 
-    def _own_texture_grad(self):
-        # the persistent texel-gradient buffer (replaced by a flat-buffer slice when GradSync takes over).  With the
-        # fused render a second one: step k's raster backward accumulates into one and zeroes the other
-        # (gstex_raster_bwd zero_buf), which step k + 1 accumulates into, so no forward spends its grid zeroing 120 MB
-        self._tex_grad = torch.zeros_like(self.texture_dc)
-        # (not under GradSync, whose flat-buffer slice is the sink: the second buffer would never be used)
-        self._tex_grad_next = (torch.zeros_like(self.texture_dc)
-                               if self.fused_step and self.texture_grad_route is None else None)
-        self._cur_zeroed = True  # the current buffer holds no gradient
-        self._next_zeroed = self._tex_grad_next is not None
-        self.texture_dc.grad = self._tex_grad
-        self.texture_grad_sink = self._tex_grad
-
-    def _double_buffered(self) -> bool:
-        return (self._tex_grad_next is not None and self.texture_grad_route is None
-                and self.texture_grad_sink is self._tex_grad)
+    @property
+    def texture_grad_sink(self):
+        """The buffer the raster backward accumulates the texel gradient into (None: autograd owns it)."""
+        return self.texel_grad.sink
 
     def _step_texels(self, buf, only, skip_flag):
         """The deferred texel update reading `buf` (the gradient buffer of the step it belongs to)."""
         keep = self.texture_dc.grad
         self.texture_dc.grad = buf
         try:
-            self._step(only=only, skip_flag=skip_flag)
+            self.optimizer.step(only=only, skip_flag=skip_flag)
         finally:
             self.texture_dc.grad = keep
 
-    @property
-    def texture_grad_zeroed_by_update(self) -> bool:
-        """The texel gradient buffer handed to the raster (texture_grad_sink) is zeroed by the raster forward
-        (gstex_raster_fwd zero_buf) before the backward accumulates into it: a gradient-buffer owner
-        (gstex_amd.dist.GradSync) must not fill that slice itself (with the deferred texel update, defer_texture, that
-        fill would also pre-empt the update still reading it)."""
-        return True
-
     def reset_texture_grad(self):
-        """Zero the texel-gradient sink lazily: the next differentiable render's raster forward zeroes it before its
-        backward accumulates (gstex_raster_fwd zero_buf).  Called by zero_grad() and by gstex_amd.dist.GradSync.zero(), so
-        a gradient left by a backward whose step was skipped never leaks into the next step."""
-        self._sink_fresh = True
+        """Discard the texel-gradient sink's content lazily (zero_grad(); a skipped step's gradient): the
+        next differentiable render is the step's first again, whose raster forward zeroes the sink."""
+        self.texel_grad.reset()
 
     def _skip_flag(self):
         """The current step's guard flag (1-element view of step_control) for its Adam launches, or None."""
@@ -299,6 +265,21 @@ class GStexTrainer:
         fn, self._pending_tex = self._pending_tex, None
         if fn is not None:
             fn()
+
+    def _pending_slots(self):
+        """Where a render runs the pending texel update: -> (before_pair_wait, texture_ready) callbacks.  Without a
+        pair-count read-back (pairs) it runs here, at the render's start: ~90 us of streaming work the device starts
+        on while the host enqueues the preprocessing and binning, instead of idling after a synchronisation.  With
+        one, while the host waits for the count.  An update that first waits for its collective (GradSync) runs
+        right before the raster forward, the first reader of the texels, so the binning does not queue behind it."""
+        if self._pending_tex is None:
+            return None, None
+        if self._pending_collective:
+            return None, self._run_pending_texture
+        if self.pairs is None:
+            return self._run_pending_texture, None
+        self._run_pending_texture()
+        return None, None
 
     def wait_texture(self):
         """Order the current stream after the pending texel update (defer_texture): it is enqueued now."""
@@ -339,14 +320,9 @@ class GStexTrainer:
         get_outputs evaluates it in training and eval alike (gstex.py:1103)."""
         means = self.means
         deg = self.sh_degree_now() if sh_degree_now is None else sh_degree_now
-        if self._pending_tex is not None and not self._pending_collective and self.pairs is not None:
-            # the deferred texel update first (read-back-free step: there is no pair-count wait to fill): ~90 us of
-            # streaming work the device starts on while the host enqueues the step's short preprocessing and binning
-            # launches, instead of idling through them after a synchronisation (the bench's first timed step); it only
-            # has to land before the raster forward, the first reader of the texels
-            self._run_pending_texture()
+        before_pair_wait, texture_ready = self._pending_slots()
         if self._fused_ok(composite, geometry, view):
-            return self._render_fused(view, deg)
+            return self._render_fused(view, deg, texture_ready)
         if self.fused_activations:  # one HIP launch each way (gstex_amd.activations)
             quats, scales, opacities, uv0, umap, vmap, viewdirs = activate(
                 means, self.quats, self.scales, self.opacities, self.mappings, view.campos)
@@ -379,16 +355,11 @@ class GStexTrainer:
             rgbs = torch.sigmoid(self.features_dc)
         # SH2RGB(texture_dc) (gstex.py:1119) applied by the raster on read instead of materialised
         texture = self.texture_dc
-        # the deferred texel update: while the host waits for the pair count (one GPU: it fills the device's idle time
-        # there), or -- when it first waits for its data-parallel collective (GradSync) -- right before the raster
-        # forward, so that the binning's placement and sort do not queue behind that wait
-        pend = self._pending_tex is not None
-        late = pend and self._pending_collective
-        sink, zero_sink, on_grad = self._texel_grad_target()
+        sink, zero_sink, first, on_grad, _ = self.texel_grad.target(fused=False)
         guard = None
         if self.pairs is not None and torch.is_grad_enabled():
             self._poll_pairs()
-            guard = (self.pairs, self._skip_flag(), self._sink_fresh, self.step)
+            guard = (self.pairs, self._skip_flag(), first, self.step)
         img, depth, reg, alpha, tex, normal = ops.texture_gaussians(
             (n, 1, 3), self.texture_dims, centers, extents, depths, nth, rgbs, opacities, means, scales, 1, quats,
             uv0, umap, vmap, texture, view.viewmat, view.c2w, view.fx, view.fy, view.cx, view.cy, view.H, view.W,
@@ -396,12 +367,9 @@ class GStexTrainer:
             texture_transform=(SH_C0, 0.5), fold_aabb=True,  # centers come from get_aabb_2d just above
             geometry_outputs=self.geometry_outputs if geometry is None else geometry,
             texture_grad_sink=sink, zero_texture_grad_sink=zero_sink, on_texture_grad=on_grad,
-            texture_ready=self._run_pending_texture if late else None,
-            before_pair_wait=self._run_pending_texture if pend and not late else None,
-            pair_guard=guard)
+            texture_ready=texture_ready, before_pair_wait=before_pair_wait, pair_guard=guard)
         if torch.is_grad_enabled():
-            self._sink_fresh = False  # zeroed by this forward: further renders before the step accumulate on top
-            self._cur_zeroed = False
+            self.texel_grad.rendered()
         out = dict(img=img, tex=tex, depth=depth, reg=reg, alpha=alpha, normal=normal)
         if composite:
             out["rgb"] = _composite(img, tex, alpha, self.background)
@@ -411,13 +379,6 @@ class GStexTrainer:
         """fix_init (gstex.py:209, the DTU configs): the SH basis is evaluated at (x, -z, y) (gstex.py:1104-1108)."""
         swap = self.fix_init and self.sh_degree > 0
         return torch.stack([viewdirs[:, 0], -viewdirs[:, 2], viewdirs[:, 1]], -1) if swap else viewdirs
-
-    def _texel_grad_target(self):
-        """(sink, zero_sink, on_grad) of a render: GradSync's route (the flat buffer's slice, or its side buffer once
-        the tail's collective is on the wire) for a render that records a backward, else the trainer's own sink."""
-        if self.texture_grad_route is not None and torch.is_grad_enabled():
-            return self.texture_grad_route(self._sink_fresh)
-        return self.texture_grad_sink, self._sink_fresh, self.texture_grad_ready
 
     def _fused_ok(self, composite: bool, geometry, view: View | None = None) -> bool:
         """Whether render() takes gstex_amd.fused's path (see its docstring for why each condition is there).  A view
@@ -430,21 +391,12 @@ class GStexTrainer:
                 and torch.is_grad_enabled() and not torch.are_deterministic_algorithms_enabled()
                 and not torch.cuda.is_current_stream_capturing())
 
-    def _render_fused(self, view: View, deg: int):
+    def _render_fused(self, view: View, deg: int, texture_ready=None):
         from . import fused
 
-        sink, zero_sink, on_grad = self._texel_grad_target()  # (as the per-op render)
-        # a deferred texel update that first waits for its collective (GradSync) runs right before the raster forward
-        late = self._run_pending_texture if self._pending_tex is not None and self._pending_collective else None
-        zero_next = None
-        if self._double_buffered():
-            zero_sink = zero_sink and not self._cur_zeroed  # (zeroed by the previous step's raster backward)
-            zero_next = None if self._next_zeroed else self._tex_grad_next  # this backward zeroes the other buffer
         self._poll_pairs()
-        img, alpha, tex = fused.train_render(self, view, deg, sink, zero_sink, self._sink_fresh, on_grad, late,
-                                             zero_next)
-        self._sink_fresh = False
-        self._cur_zeroed = False
+        img, alpha, tex = fused.train_render(self, view, deg, self.texel_grad.target(fused=True), texture_ready)
+        self.texel_grad.rendered()
         depth, reg, normal = ops._zero_views(self.device, int(view.H), int(view.W))  # not rendered, as the per-op path
         return dict(img=img, tex=tex, depth=depth, reg=reg, alpha=alpha, normal=normal)
 
@@ -697,52 +649,29 @@ class GStexTrainer:
         of the step: the texel group is updated as soon as its collective lands, overlapping the head's collective,
         and the 1 / world averaging rides in the fused update (GradSync.all_reduce_and_step); otherwise call
         sync.all_reduce() before this."""
-        self._sink_fresh = True  # the next step's first render zeroes the texel-gradient sink
         sf = self._skip_flag()  # this step's pair-capacity guard (None without pair_capacity)
-        if self.defer_texture:
-            self._run_pending_texture()  # (two steps without a render in between)
-            tex = {id(self.texture_dc)}
+        opt, tex, defer = self.optimizer, {id(self.texture_dc)}, self.defer_texture
+        self._run_pending_texture()  # (two steps without a render in between)
+        buf = self.texel_grad.stepped()  # the gradient this step's texel update reads (the next step's may differ)
+        if not self.fused_adam:  # (torch's Adam: no skip_flag, which needs the fused one)
             if sync is not None:
-                # the texel update in pieces, each as soon as its piece of the collective has landed (GradSync)
-                rng = (lambda s, lo, hi, first: self.optimizer.step_range(self.texture_dc, lo, hi, first,
-                                                                          grad_scale=s, skip_flag=sf)) \
-                    if self.fused_adam else None
-                self._pending_tex = sync.all_reduce_and_step(
-                    lambda s: self.optimizer.step(only=tex, grad_scale=s, skip_flag=sf),
-                    lambda s: self.optimizer.step(skip=tex, grad_scale=s, skip_flag=sf), defer_tail=True,
-                    step_tail_range=rng)
-                self._pending_collective = True
-            else:
-                self._step(skip=tex, skip_flag=sf)
-                buf = self.texture_dc.grad
-                self._pending_tex = lambda: self._step_texels(buf, tex, sf)
-                self._pending_collective = False
-                if self._double_buffered():
-                    # the next step accumulates into the other buffer (zeroed by this step's raster backward, or
-                    # else by the next forward); the pending update reads this one
-                    self._tex_grad, self._tex_grad_next = self._tex_grad_next, self._tex_grad
-                    self._cur_zeroed, self._next_zeroed = self._next_zeroed, False
-                    self.texture_dc.grad = self._tex_grad
-                    self.texture_grad_sink = self._tex_grad
-            self.step += 1
-            return
-        if sync is not None and self.fused_adam:
-            tex = {id(self.texture_dc)}
-            sync.all_reduce_and_step(lambda s: self.optimizer.step(only=tex, grad_scale=s, skip_flag=sf),
-                                     lambda s: self.optimizer.step(skip=tex, grad_scale=s, skip_flag=sf))
-            self.step += 1
-            return
-        if sync is not None:
-            sync.all_reduce()
-        self._step(skip_flag=sf)
+                sync.all_reduce()
+            opt.step()
+        elif sync is not None:
+            # the texel update in pieces, each as soon as its piece of the collective has landed (GradSync)
+            rng = (lambda s, lo, hi, first: opt.step_range(self.texture_dc, lo, hi, first, grad_scale=s,
+                                                           skip_flag=sf)) if defer else None
+            self._pending_tex = sync.all_reduce_and_step(
+                lambda s: opt.step(only=tex, grad_scale=s, skip_flag=sf),
+                lambda s: opt.step(skip=tex, grad_scale=s, skip_flag=sf), defer_tail=defer, step_tail_range=rng)
+            self._pending_collective = defer
+        elif defer:
+            opt.step(skip=tex, skip_flag=sf)
+            self._pending_tex = lambda: self._step_texels(buf, tex, sf)
+            self._pending_collective = False
+        else:
+            opt.step(skip_flag=sf)
         self.step += 1
-
-    def _step(self, **kw):
-        """optimizer.step with the fused optimizer's extensions (skip_flag is None without pair_capacity, which needs
-        the fused Adam)."""
-        if kw.get("skip_flag") is None:
-            kw.pop("skip_flag", None)
-        self.optimizer.step(**kw)
 
     def zero_grad(self, set_to_none: bool = True):
         """Optimizers.zero_grad_all (engine/optimizers.py): torch's default set_to_none=True, so backward
@@ -794,7 +723,7 @@ class GStexTrainer:
                     "exp_avg_sq": torch.zeros_like(self.texture_dc),
                 }
             if self.defer_texture:  # a fresh persistent gradient buffer (GradSync replaces it)
-                self._own_texture_grad()
+                self.texel_grad.own(self.texture_dc, self.fused_step)
         else:
             st = self.optimizer.state.get(old)
             if st:

@@ -10,6 +10,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from gstex_amd.dist import GradSync
+from gstex_amd.texel_grad import TexelGrad
 
 
 def _free_port():
@@ -87,10 +88,7 @@ class _SinkTrainer:
         self.means, self.features_dc, self.features_rest = P(n, 3), P(n, 3), P(n, 15, 3)
         self.opacities, self.scales, self.quats = P(n, 1), P(n, 3), P(n, 4)
         self.texture_dc = P(n_tex, 3)
-        self.texture_grad_sink = None
-        self.texture_grad_ready = None
-        self.texture_grad_route = None
-        self._fresh = True
+        self.texel_grad = TexelGrad()  # (the trainer's own class, over CPU tensors)
 
     def parameters(self):
         return [self.means, self.features_dc, self.features_rest, self.opacities, self.scales, self.quats,
@@ -108,15 +106,14 @@ class _SinkTrainer:
         loss = w * (self.means.sum() + self.features_rest.sum() + 2 * self.opacities.sum() + self.scales.sum()
                     + self.quats.sum())
         loss.backward()  # features_dc unused under SH colour, like the real step
-        assert self.texture_grad_sink is not None, "GradSync must hand the texel slice to the raster backward"
-        if self.texture_grad_route is not None and scale != 1.0:
-            # several renders in one step (GStexTrainer.render): the per-render target, zeroed by its first render
-            sink, zero, ready = self.texture_grad_route(self._fresh)
-            self._fresh = False
-            if zero:
-                sink.zero_()
-        else:
-            sink, ready = self.texture_grad_sink, self.texture_grad_ready
+        assert self.texel_grad.sink is not None, "GradSync must hand the texel slice to the raster backward"
+        # scale != 1: several renders in one step (GStexTrainer.render), each with GradSync's per-render target; else
+        # straight into the slice with its ready callback (what TexelGrad.target gives without grad enabled)
+        with torch.set_grad_enabled(scale != 1.0):
+            sink, zero, _, ready, _ = self.texel_grad.target(fused=False)
+        self.texel_grad.rendered()
+        if zero:  # (the raster forward's zero_buf: GradSync.zero() leaves the slice to the step's first render)
+            sink.zero_()
         sink.add_(w * self.texture_dc.detach())  # the kernel's accumulation
         if ready is not None:
             ready()
@@ -255,8 +252,7 @@ def _trainer_worker(rank, world, port, q):
         sync4 = GradSync(tr4, world)
         for step in range(2):
             sync4.zero()
-            tr4._fresh = True
-            tr4.backward(rank, scale=1.0 + 1e-9)  # (scale != 1: through texture_grad_route)
+            tr4.backward(rank, scale=1.0 + 1e-9)  # (scale != 1: through GradSync's route)
             started = sync4._work is not None
             tr4.backward(rank, scale=2.0)
             tr4.backward(rank, scale=3.0)

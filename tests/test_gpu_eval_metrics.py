@@ -190,8 +190,8 @@ def test_evaluate_leaves_the_training_state_alone(scene):
         grads = [p.grad for p in params]
         before = dict(step=tr.step, params=[p.detach().clone() for p in params],
                       grads=[None if g is None else g.clone() for g in grads], background=tr.background.clone(),
-                      gen=tr._background_gen.get_state().clone(), sink_fresh=tr._sink_fresh,
-                      zeroed=(tr._cur_zeroed, tr._next_zeroed), skipped=list(tr.skipped_steps),
+                      gen=tr._background_gen.get_state().clone(), texel_grad=tr.texel_grad.state(),
+                      skipped=list(tr.skipped_steps),
                       capacity=None if tr.pairs is None else tr.pairs.capacity, control=tr.step_control.clone())
         res = tr.evaluate(view, image)
         assert torch.isfinite(res.metrics).all()
@@ -203,7 +203,7 @@ def test_evaluate_leaves_the_training_state_alone(scene):
         assert any(g is not None and float(g.abs().max()) > 0 for g in grads)
         assert torch.equal(tr.background, before["background"])
         assert torch.equal(tr._background_gen.get_state(), before["gen"])
-        assert tr._sink_fresh == before["sink_fresh"] and (tr._cur_zeroed, tr._next_zeroed) == before["zeroed"]
+        assert tr.texel_grad.state() == before["texel_grad"]
         assert tr.skipped_steps == before["skipped"]
         assert (None if tr.pairs is None else tr.pairs.capacity) == before["capacity"]
         assert torch.equal(tr.step_control, before["control"])

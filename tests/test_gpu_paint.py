@@ -340,7 +340,7 @@ def training_state(tr):
         for k, v in s.items():
             st[f"adam {id(p)} {k}"] = v.detach().clone() if isinstance(v, torch.Tensor) else v
     st["step"] = tr.step
-    st["sink_fresh"] = tr._sink_fresh
+    st["texel_grad"] = tr.texel_grad.state()
     st["sink"] = None if tr.texture_grad_sink is None else tr.texture_grad_sink.detach().clone()
     return st
 

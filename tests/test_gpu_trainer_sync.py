@@ -2,6 +2,7 @@
 buffer, the raster backward accumulating the texel gradient straight into its slice, the tail collective
 started from the backward -- must train exactly like the un-synced step, across an in-place rechart.
 (World size > 1 is covered on CPU by tests/test_dist.py; the driver runs the 8-GPU bench.)"""
+import gc
 import os
 import socket
 
@@ -32,6 +33,11 @@ def _assert_trains_alike(name, a, b, what):
     d = (a - b).abs()
     err, mean = float(d.max()) / scale, float(d.mean()) / scale
     assert float(d.max()) <= LRS[name] and mean < 1e-6, f"{name}: {what} differs (max {err:.2e}, mean {mean:.2e})"
+
+
+def _other_buffer(tr):
+    """A double-buffered trainer's non-current texel-gradient buffer: what its next fused raster backward zeroes."""
+    return tr.texel_grad.target(fused=True)[4]
 
 
 def test_synced_step_matches_unsynced_across_rechart():
@@ -125,7 +131,7 @@ def test_deferred_texture_update_across_rechart_and_eval():
         # the persistent texel-gradient buffers hold the last gradient until the next differentiable raster forward
         # zeroes them (gstex_raster_fwd zero_buf), before its backward accumulates into them; a fused-render trainer keeps
         # it in the second buffer of its pair (the current one was zeroed by the last raster backward)
-        last = alone._tex_grad_next if alone._tex_grad_next is not None else alone.texture_dc.grad
+        last = _other_buffer(alone) if alone.texel_grad.double_buffered else alone.texture_dc.grad
         assert float(last.abs().max()) > 0.0
         for tr in (alone, synced):
             tr.render(views[0])
@@ -182,7 +188,7 @@ def test_deferred_texture_update_matches_plain_step():
         # the persistent texel-gradient buffers hold the last gradient until the next differentiable raster forward
         # zeroes them (gstex_raster_fwd zero_buf); a fused-render trainer keeps it in the second buffer of its pair (the
         # current one was zeroed by the last raster backward, gstex_raster_bwd zero_buf)
-        last = alone._tex_grad_next if alone._tex_grad_next is not None else alone.texture_dc.grad
+        last = _other_buffer(alone) if alone.texel_grad.double_buffered else alone.texture_dc.grad
         assert float(last.abs().max()) > 0.0
         for tr in (alone, synced):
             tr.render(views[0])
@@ -294,7 +300,9 @@ def test_pair_capacity_step_trains_like_the_readback_step():
             for tr in (sync, capd):
                 tr.pixel_num = 1.3 * tr.texture_dc.shape[0]
                 tr.recharge()
-    # a step in capacity mode, with every host-synchronising call counted
+    # a step in capacity mode, with every host-synchronising call counted (earlier tests' trainers first: one in a
+    # reference cycle with its GradSync is freed whenever the collector runs, and PairCapacity.__del__ synchronises)
+    gc.collect()
     calls = []
 
     def spy(name, fn):
@@ -393,7 +401,7 @@ def test_fused_overflow_does_not_skip_later_steps():
     gt = torch.rand((96, 96, 3), generator=torch.Generator().manual_seed(10)).to(dev)
     tr = GStexTrainer(sc, dev, start_step=3000, defer_texture=True)
     tr.pairs = ops.PairCapacity(dev, capacity=1000)  # far below this scene's ~20k pairs
-    assert tr._fused_ok(False, None) and tr._double_buffered()
+    assert tr._fused_ok(False, None) and tr.texel_grad.double_buffered
 
     def step():
         tr.zero_grad()
