@@ -151,6 +151,29 @@ class GstexPaintBlendArgs(ctypes.Structure):
                 ("shift", c_float)]
 
 
+class GstexDensityPlanArgs(ctypes.Structure):
+    """gstex_density_plan_args (added within ABI 19): one density-control event's decisions."""
+    _fields_ = [("n", c_int32), ("size_prune", c_int32), ("prune_only", c_int32)] + [
+        (name, c_float) for name in ("grad_threshold", "log_big", "logit_faint", "max_screen_px", "log_world",
+                                     "log_split")] + [
+        (name, c_void_p) for name in ("log_scales", "opac_logits", "grad_sum", "count", "max_extent", "rows", "kind")]
+
+
+class GstexDensityTensor(ctypes.Structure):
+    """gstex_density_tensor (added within ABI 19): one per-splat tensor of gstex_density_apply."""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("width", c_int32), ("role", c_int32)]
+
+
+class GstexDensityApplyArgs(ctypes.Structure):
+    """gstex_density_apply_args (added within ABI 19)."""
+    _fields_ = [("n", c_int32), ("n_tensors", c_int32), ("n_new", c_int64), ("log_split", c_float)] + [
+        (name, c_void_p) for name in ("rows", "kind", "offsets", "scales", "quats_n", "noise")] + [
+        ("tensors", POINTER(GstexDensityTensor))]
+
+
+DENSITY_KEEP, DENSITY_CLONE, DENSITY_SPLIT, DENSITY_PRUNE = 0, 1, 2, 3  # GSTEX_DENSITY_*
+DENSITY_ROLE_COPY, DENSITY_ROLE_MOMENT, DENSITY_ROLE_MEANS, DENSITY_ROLE_LOG_SCALES = 0, 1, 2, 3  # GSTEX_DENSITY_ROLE_*
+DENSITY_MAX_TENSORS = 24  # GSTEX_DENSITY_MAX_TENSORS
 GT_F32, GT_U8 = 0, 1  # GSTEX_GT_*
 MASK_F32, MASK_BOOL = 0, 1  # GSTEX_MASK_*
 ADAM_ZERO_GRAD = 1  # GSTEX_ADAM_ZERO_GRAD
@@ -229,6 +252,9 @@ SIGNATURES = {
     "gstex_train_prologue": (c_int32, [POINTER(GstexTrainPrologueArgs), _P]),
     "gstex_train_prologue_scan_bytes": (c_size_t, [c_int32]),
     "gstex_train_epilogue": (c_int32, [POINTER(GstexTrainEpilogueArgs), _P]),
+    "gstex_density_accum": (c_int32, [c_int32, _P, _P, _CAM, _P, _P, _P, _P, _P, _P, _P]),
+    "gstex_density_plan": (c_int32, [POINTER(GstexDensityPlanArgs), _P]),
+    "gstex_density_apply": (c_int32, [POINTER(GstexDensityApplyArgs), _P]),
 }
 
 _lib = None

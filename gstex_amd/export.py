@@ -72,6 +72,36 @@ def export_ply(trainer, path) -> None:
                      "red": rgb[:, 0], "green": rgb[:, 1], "blue": rgb[:, 2]}, binary=True)
 
 
+def export_2dgs_ply(trainer, path) -> None:
+    """A one-texel trainer (the geometry stage's result, gstex_amd.density) as the 2DGS checkpoint PLY that
+    gstex_amd.init.scene_from_2dgs_ply reads: float columns x y z, nx ny nz (zeros), f_dc_0..2 (each splat's texel, the
+    SH-DC colour; under SH colour the features_dc parameter is replaced by the texture), f_rest_* channel-major,
+    opacity (logit), scale_0 scale_1 (log; the unused third column is not part of the format, the reader appends
+    ones) and rot_0..3 (raw, wxyz).  Anything but one texel per splat raises ValueError."""
+    from .ply import write_ply
+
+    n = int(trainer.means.shape[0])
+    dims = trainer.texture_dims.detach().cpu()
+    want = torch.ones((n, 3), dtype=dims.dtype)
+    want[:, 2] = torch.arange(n, dtype=dims.dtype)
+    if trainer.n_texels != n or tuple(dims.shape) != (n, 3) or not torch.equal(dims, want):
+        raise ValueError("export_2dgs_ply: a 2DGS checkpoint has one colour per splat; this trainer's charts hold "
+                         f"{trainer.n_texels} texels for {n} splats")
+    c = lambda t: t.detach().cpu().numpy().astype(np.float32)  # noqa: E731
+    xyz, dc, op = c(trainer.means), c(trainer.texels()[:n]), c(trainer.opacities).reshape(n)
+    rest = c(trainer.features_rest.detach().transpose(1, 2).reshape(n, -1)) if trainer.features_rest.numel() else \
+        np.zeros((n, 0), np.float32)
+    ls, q = c(trainer.scales), c(trainer.quats)
+    zeros = np.zeros(n, np.float32)
+    cols = {"x": xyz[:, 0], "y": xyz[:, 1], "z": xyz[:, 2], "nx": zeros, "ny": zeros, "nz": zeros}
+    cols.update({f"f_dc_{k}": dc[:, k] for k in range(3)})
+    cols.update({f"f_rest_{k}": rest[:, k] for k in range(rest.shape[1])})
+    cols["opacity"] = op
+    cols.update({f"scale_{k}": ls[:, k] for k in range(2)})
+    cols.update({f"rot_{k}": q[:, k] for k in range(4)})
+    write_ply(path, {k: np.ascontiguousarray(v) for k, v in cols.items()}, binary=True)
+
+
 def trainer_from_npz(path, device, **trainer_kwargs):
     """A GStexTrainer holding exactly the exported parameters (fresh optimizer state)."""
     from .model import GStexTrainer

@@ -136,6 +136,7 @@ class _TrainRender(torch.autograd.Function):
         ctx.zero_next = zero_next
         ctx.save_for_backward(quats, log_scales)
         ctx.set_materialize_grads(False)
+        tr._last_vis = (arena, off["num_tiles_hit"], off["extents"], n)  # (GStexTrainer.last_visibility)
         img = _view(arena, off["img"], (H, W, 3))
         alpha = _view(arena, off["alpha"], (H, W))
         tex = _view(arena, off["tex"], (H, W, C))

@@ -190,6 +190,10 @@ class GStexTrainer:
         # scatter touched) and the per-splat scratch of its depth render
         self._paint_acc = None
         self._paint_scratch = {}
+        # last_visibility: (num_tiles_hit, extents) of the last differentiable render, on either render path -- what
+        # the density controller's per-step statistics read (gstex_amd.density).  Kept as the tensors themselves (per-op
+        # render) or as (arena, two byte offsets, n) (fused render: the views are made when somebody asks)
+        self._last_vis = None
         # defer_texture (not in the reference; fused Adam on a HIP device): the texel parameter's Adam update of step k
         # (73 % of the parameters at cfg3) runs in step k+1, before the raster forward, from a persistent gradient
         # buffer the raster grids zero (DESIGN.md "The texel gradient's life cycle"; the slots: _pending_slots).
@@ -224,6 +228,16 @@ class GStexTrainer:
         if self.defer_texture:
             self.texel_grad.own(self.texture_dc, self.fused_step)
         self._build_optimizer()
+
+    @property
+    def last_visibility(self):
+        """(num_tiles_hit (n,) int32, extents (n, 2)) of the last differentiable render since zero_grad(), or None."""
+        v = self._last_vis
+        if v is None or len(v) == 2:
+            return v
+        arena, o_nth, o_ext, n = v
+        return (arena[o_nth:o_nth + 4 * n].view(torch.int32),
+                arena[o_ext:o_ext + 8 * n].view(torch.float32).view(n, 2))
 
     @property
     def texture_grad_sink(self):
@@ -370,6 +384,7 @@ class GStexTrainer:
             texture_ready=texture_ready, before_pair_wait=before_pair_wait, pair_guard=guard)
         if torch.is_grad_enabled():
             self.texel_grad.rendered()
+            self._last_vis = (nth, extents)
         out = dict(img=img, tex=tex, depth=depth, reg=reg, alpha=alpha, normal=normal)
         if composite:
             out["rgb"] = _composite(img, tex, alpha, self.background)
@@ -684,6 +699,7 @@ class GStexTrainer:
         if self._pending_tex is not None and not self._pending_collective:
             self._run_pending_texture()
         self.reset_texture_grad()
+        self._last_vis = None  # (it holds the last fused render's arena: released before the next one is made)
         if self.defer_texture:
             keep = self.texture_dc.grad
             self.optimizer.zero_grad(set_to_none=set_to_none)
@@ -734,3 +750,113 @@ class GStexTrainer:
         self.n_texels = n_new
         self.mappings.copy_(mappings)
         return new_dims
+
+    # ------------------------------------------------------------------ density control
+    @torch.no_grad()
+    def apply_density(self, grad_sum, count, max_extent, noise, thresholds: dict, size_prune: bool,
+                      max_splats: int | None = None):
+        """One density-control event (gstex_amd.density; DESIGN.md "Density control"): plan from the statistics
+        (three (n,) fp32 arrays) and `thresholds` (density_thresholds), scan, one read-back, then every per-splat
+        parameter and the Adam moments the optimizer holds scattered into fresh tensors of n_new rows in source order
+        (kept rows keep their moments, clone rows and split children start at zero; each parameter's step count is
+        kept, as in recharge()).  noise: (n, 2, 2), the split children's offsets in units of the activated scales.
+        Defined on one-texel charts only (ValueError otherwise); a trainer under GradSync raises.  Rebuilt for n_new:
+        geometry_flat and its four views, features_dc / features_rest / texture_dc, texture_dims, n_texels, mappings,
+        the optimizer's groups and state, the texel gradient's buffers; the paint accumulator and scratch are dropped.
+        An event that would leave no splat raises RuntimeError and an all-keep event returns, both with the trainer
+        untouched.  On a CPU trainer the eager twins run instead of the kernels.  -> the DensityPlan."""
+        from . import density as dn
+
+        n, d = self.means.shape[0], self.device
+        if self.texel_grad.routed:
+            raise RuntimeError("apply_density: multi-GPU density control (a trainer under GradSync) is not supported")
+        one_texel = ("density control is defined on one-texel charts only (n_texels == n, texture_dims rows "
+                     "(1, 1, i)): run it before the first rechart onto a texel budget")
+        if self.n_texels != n or tuple(self.texture_dims.shape) != (n, 3) or self.texture_dc.shape[0] < n:
+            raise ValueError(f"apply_density: {one_texel} (n = {n}, n_texels = {self.n_texels})")
+        for name, t in (("grad_sum", grad_sum), ("count", count), ("max_extent", max_extent)):
+            if tuple(t.shape) != (n,) or t.dtype != torch.float32 or t.device != self.means.device:
+                raise ValueError(f"apply_density: {name} must be a float32 ({n},) tensor on {self.means.device}")
+        if tuple(noise.shape) != (n, 2, 2) or noise.dtype != torch.float32 or noise.device != self.means.device:
+            raise ValueError(f"apply_density: noise must be a float32 ({n}, 2, 2) tensor on {self.means.device}")
+
+        def one_texel_dims(rows):
+            dims = torch.ones((rows, 3), device=d, dtype=torch.int32)
+            dims[:, 2] = torch.arange(rows, device=d, dtype=torch.int32)
+            return dims
+
+        bad = (self.texture_dims != one_texel_dims(n)).any()  # (read back with the plan's counts)
+        plan = dn.plan_event(self.scales, self.opacities, grad_sum, count, max_extent, thresholds, size_prune,
+                             max_splats, check=bad)
+        if plan.flagged:
+            raise ValueError(f"apply_density: {one_texel}")
+        if plan.n_new == 0:
+            raise RuntimeError("apply_density: the event would prune every splat")
+        if plan.kept == n:
+            return plan
+        self.wait_texture()
+        if d.type == "cuda":
+            quats_n, scales = activate(self.means.detach(), self.quats.detach(), self.scales.detach(),
+                                       self.opacities.detach(), self.mappings, torch.zeros(3, device=d))[:2]
+        else:
+            quats_n = self.quats / self.quats.norm(dim=-1, keepdim=True)
+            s = torch.exp(self.scales[:, :-1]).clamp(min=1e-9)
+            scales = torch.cat([s, 1e-5 * s.mean(dim=-1, keepdim=True)], dim=-1)
+        opt, before = self.optimizer, self.param_groups()
+        attrs = {"xyz": "means", "features_dc": "features_dc", "features_rest": "features_rest",
+                 "opacity": "opacities", "scaling": "scales", "rotation": "quats", "texture_dc": "texture_dc"}
+        roles = {"xyz": dn.ROLE_MEANS, "scaling": dn.ROLE_LOG_SCALES}
+        named = {}
+        for group, (p,) in before.items():
+            named[group] = (p.detach()[:n], roles.get(group, dn.ROLE_COPY))  # ([:n]: the texel store has a capacity)
+            st = opt.state.get(p)
+            if st and "exp_avg" in st:
+                named[group + ".exp_avg"] = (st["exp_avg"][:n], dn.ROLE_MOMENT)
+                named[group + ".exp_avg_sq"] = (st["exp_avg_sq"][:n], dn.ROLE_MOMENT)
+        # the geometry parameters' shared allocation, segments 16-B aligned (as __init__)
+        m = plan.n_new
+        geo = [("xyz", 3), ("scaling", 3), ("rotation", 4), ("opacity", 1)]
+        flat = torch.zeros(sum((m * w + 3) // 4 * 4 for _, w in geo), device=d, dtype=torch.float32)
+        views, off = {}, 0
+        for group, w in geo:
+            views[group] = flat[off:off + m * w].view(m, w)
+            off += (m * w + 3) // 4 * 4
+
+        def alloc(name, shape):
+            v = views.get(name)
+            return v if v is not None else torch.empty(shape, device=d, dtype=torch.float32)
+
+        new = dn.apply_event(plan, named, scales, quats_n, noise, thresholds["log_split"], alloc)
+        self.geometry_flat = flat
+        for group, attr in attrs.items():
+            setattr(self, attr, torch.nn.Parameter(new[group]))
+        after = self.param_groups()
+        for g in opt.param_groups:
+            old, p = before[g["name"]][0], after[g["name"]][0]
+            g["params"] = [p]
+            st = opt.state.pop(old, None)
+            if st:
+                st = dict(st)  # (the step count is kept)
+                if "exp_avg" in st:
+                    st["exp_avg"], st["exp_avg_sq"] = new[g["name"] + ".exp_avg"], new[g["name"] + ".exp_avg_sq"]
+                opt.state[p] = st
+        self.texture_dims = one_texel_dims(m)
+        self.n_texels = m
+        self.mappings = (1.0 / (2.0 * 3.0 * torch.exp(self.scales.detach()[:, :2]))).contiguous()
+        if self.defer_texture:  # fresh persistent gradient buffers for the new texel store
+            self.texel_grad.own(self.texture_dc, self.fused_step)
+        self.texel_grad.reset()
+        self._paint_acc, self._paint_scratch, self.test_colors, self._last_vis = None, {}, None, None
+        return plan
+
+    @torch.no_grad()
+    def reset_opacity(self, value: float = 0.01):
+        """The lineage's periodic opacity reset: every opacity logit capped at logit(value), the opacity parameter's
+        two Adam moments zeroed (its step count kept).  Plain torch: it runs once per 3,000 steps."""
+        import math
+
+        self.opacities.data.clamp_(max=math.log(value / (1.0 - value)))
+        st = self.optimizer.state.get(self.opacities)
+        if st and "exp_avg" in st:
+            st["exp_avg"].zero_()
+            st["exp_avg_sq"].zero_()

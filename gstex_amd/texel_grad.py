@@ -31,6 +31,11 @@ class TexelGrad:
         return self._sink
 
     @property
+    def routed(self) -> bool:
+        """Whether a route is attached (GradSync owns the sink)."""
+        return self._route is not None
+
+    @property
     def double_buffered(self) -> bool:
         return self._other is not None
 

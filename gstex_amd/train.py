@@ -61,7 +61,7 @@ def _to_device(pair, device):
 
 
 def fit(trainer, pairs, steps: int, *, xyz_lr_final: float | None = None, max_steps: int = 15000,
-        build_chart_every: int = 100, seed: int = 0, on_step=None, pose_refiner=None) -> dict:
+        build_chart_every: int = 100, seed: int = 0, on_step=None, pose_refiner=None, density=None) -> dict:
     """Run `steps` training steps from trainer.step on.  pairs: a sequence of (View, image[, mask]) as
     gstex_amd.data.load_blender yields them, moved to the trainer's device once.  Per step s = trainer.step:
 
@@ -76,9 +76,19 @@ def fit(trainer, pairs, steps: int, *, xyz_lr_final: float | None = None, max_st
     pose_refiner.view(k, view) for the chosen pair k, adds pose_refiner.regulariser() to the loss and calls
     pose_refiner.step() after optimizer_step().  None: the loop above, unchanged.
 
+    density (a gstex_amd.density.DensityController over a one-texel trainer; the geometry stage): step 3 becomes
+    zero_grad(), forward_backward(), density.accumulate(trainer, view), optimizer_step(), density.update(trainer) --
+    the statistics read the step's gradient before Adam consumes it, an event (clone / split / prune, opacity reset)
+    runs after the update.  build_chart_every must then be 0 or None (ValueError): density control is defined on
+    one-texel charts.  The returned dict gains density, the list of the events' records.  None: the loop above,
+    unchanged.
+
     Returns loss (a (steps,) device tensor, filled without a read-back), views (the chosen indices) and recharts
     (the steps s after which a rechart ran).  The only host synchronisation is inside a rechart (build_charts'
     bisection reads its score back)."""
+    if density is not None and build_chart_every:
+        raise ValueError(f"fit: density control needs build_chart_every = 0 or None (got {build_chart_every}): it is "
+                         "defined on one-texel charts, which a rechart replaces")
     pairs = [_to_device(p, trainer.device) for p in pairs]
     if not pairs:
         raise ValueError("fit: no (view, image) pairs")
@@ -86,7 +96,7 @@ def fit(trainer, pairs, steps: int, *, xyz_lr_final: float | None = None, max_st
     schedule = None if xyz_lr_final is None else exponential_decay(trainer.lrs["xyz"], xyz_lr_final, max_steps)
     gen = torch.Generator().manual_seed(int(seed))
     losses = torch.zeros(int(steps), device=trainer.device, dtype=torch.float32)
-    order, views, recharts = [], [], []
+    order, views, recharts, events = [], [], [], []
     for i in range(int(steps)):
         s = trainer.step
         if schedule is not None:
@@ -98,12 +108,18 @@ def fit(trainer, pairs, steps: int, *, xyz_lr_final: float | None = None, max_st
         trainer.zero_grad()
         if pose_refiner is None:
             out = trainer.forward_backward(view, image, mask)
-            trainer.optimizer_step()
         else:
-            out = trainer.forward_backward(pose_refiner.view(k, view), image, mask,
-                                           extra_loss=pose_refiner.regulariser())
-            trainer.optimizer_step()
+            view = pose_refiner.view(k, view)
+            out = trainer.forward_backward(view, image, mask, extra_loss=pose_refiner.regulariser())
+        if density is not None:
+            density.accumulate(trainer, view)
+        trainer.optimizer_step()
+        if pose_refiner is not None:
             pose_refiner.step()
+        if density is not None:
+            event = density.update(trainer)
+            if event is not None:
+                events.append(event)
         losses[i].copy_(out.loss)
         views.append(k)
         if build_chart_every and s % build_chart_every == 0:
@@ -111,4 +127,7 @@ def fit(trainer, pairs, steps: int, *, xyz_lr_final: float | None = None, max_st
             recharts.append(s)
         if on_step is not None:
             on_step(s, out)
-    return dict(loss=losses, views=views, recharts=recharts)
+    res = dict(loss=losses, views=views, recharts=recharts)
+    if density is not None:
+        res["density"] = events
+    return res

@@ -691,6 +691,86 @@ typedef struct gstex_train_epilogue_args {
 } gstex_train_epilogue_args;
 int gstex_train_epilogue(const gstex_train_epilogue_args* args, void* stream);
 
+/* ---- adaptive density control -- added within ABI 19 (additive); not in the reference, which disables it ----------
+ * Clone, split and prune of one-texel splats while training (3DGS section 5.2 as 2DGS uses it; DESIGN.md "Density
+ * control").  Every value below is computed by individually rounded fp32 + - * / sqrt in the order DESIGN.md states,
+ * and every decision compares against thresholds the host formed, so gstex_amd.density's eager twins reproduce the
+ * three entry points bit for bit.
+ *
+ * gstex_density_accum: one launch per training step, after the backward.  For every splat with num_tiles_hit > 0:
+ * grad_sum += |dL/d(NDC centre)| (from v_means = dL/dmeans, cam->viewmat, fx, fy, H, W), count += 1, max_extent =
+ * max(max_extent, extents[i][0], extents[i][1]).  num_tiles_hit / extents: the step's render's (gstex_preprocess or
+ * gstex_train_prologue outputs).  skip (nullable): the step's pair-guard flag; non-zero makes the launch a no-op on
+ * the device, like gstex_adam_step's skip.  Only cam's viewmat, fx, fy, H and W are read. */
+int gstex_density_accum(int32_t n, const float* means, const float* v_means, const gstex_camera* cam,
+                        const int32_t* num_tiles_hit, const float* extents, const float* skip,
+                        float* grad_sum, float* count, float* max_extent, void* stream);
+
+/* kind[i] written by gstex_density_plan; rows[i] = 1 (KEEP), 2 (CLONE: the splat then its copy; SPLIT: two children
+ * and no parent) or 0 (PRUNE). */
+#define GSTEX_DENSITY_KEEP 0
+#define GSTEX_DENSITY_CLONE 1
+#define GSTEX_DENSITY_SPLIT 2
+#define GSTEX_DENSITY_PRUNE 3
+/* With m = max(log_scales[i][0], log_scales[i][1]); hot = count > 0 && grad_sum >= grad_threshold * count (false for
+ * every splat when prune_only); big = m > log_big; faint = opac_logits[i] < logit_faint.  First match wins:
+ *   faint -> PRUNE;  hot && big -> SPLIT, or PRUNE when size_prune && m - log_split > log_world;
+ *   size_prune && (max_extent > max_screen_px || m > log_world) -> PRUNE;  hot -> CLONE;  otherwise KEEP.
+ * The thresholds are fp32 values the host formed: log_big = log(percent_dense * extent), logit_faint =
+ * logit(min_opacity), log_world = log(0.1 * extent), log_split = log(1.6); all must be finite. */
+typedef struct gstex_density_plan_args {
+    int32_t n;
+    int32_t size_prune;
+    int32_t prune_only;
+    float grad_threshold;
+    float log_big;
+    float logit_faint;
+    float max_screen_px;
+    float log_world;
+    float log_split;
+    const float* log_scales;  /* (n, 3) */
+    const float* opac_logits; /* (n) */
+    const float* grad_sum;
+    const float* count;
+    const float* max_extent;
+    int32_t* rows;
+    int32_t* kind;
+} gstex_density_plan_args;
+int gstex_density_plan(const gstex_density_plan_args* args, void* stream);
+
+/* One per-splat tensor of gstex_density_apply: src (n, width) scattered into dst (n_new, width), splat i's rows at
+ * offsets[i] (the exclusive scan of rows: gstex_scan_offsets), in source order.  role COPY: every row is the source
+ * row.  MOMENT (an Adam moment): a KEEP row and a CLONE's first row are the source row, a CLONE's second row and both
+ * SPLIT children are zero.  MEANS (width 3): as COPY, but SPLIT child k of splat i gets, per component c,
+ * mean[c] + ((R[c][0] * (s_u * z_k0)) + (R[c][1] * (s_v * z_k1))) with s = scales[i] (activated), R the rotation of
+ * quats_n[i] and z = noise[i] (2, 2).  LOG_SCALES (width >= 2): as COPY, but the first two columns of SPLIT children
+ * are log_s - log_split. */
+#define GSTEX_DENSITY_ROLE_COPY 0
+#define GSTEX_DENSITY_ROLE_MOMENT 1
+#define GSTEX_DENSITY_ROLE_MEANS 2
+#define GSTEX_DENSITY_ROLE_LOG_SCALES 3
+#define GSTEX_DENSITY_MAX_TENSORS 24
+typedef struct gstex_density_tensor {
+    const float* src;
+    float* dst;
+    int32_t width; /* floats per splat row; 0 = skipped */
+    int32_t role;
+} gstex_density_tensor;
+typedef struct gstex_density_apply_args {
+    int32_t n;
+    int32_t n_tensors;
+    int64_t n_new;          /* offsets[n] as the host read it: rows of every dst; nothing is written past them */
+    float log_split;
+    const int32_t* rows;
+    const int32_t* kind;
+    const int32_t* offsets;
+    const float* scales;    /* (n, 3) activated, gstex_activate_fwd; needed by a MEANS tensor */
+    const float* quats_n;   /* (n, 4) normalised, gstex_activate_fwd; needed by a MEANS tensor */
+    const float* noise;     /* (n, 2, 2); needed by a MEANS tensor */
+    const gstex_density_tensor* tensors; /* HOST array of n_tensors entries */
+} gstex_density_apply_args;
+int gstex_density_apply(const gstex_density_apply_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
