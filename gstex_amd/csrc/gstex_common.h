@@ -4,7 +4,7 @@
 // restates each function below op-for-op (the library is compiled with -ffp-contract=off, so no
 // fused multiply-adds are formed), which is what makes the threshold decisions of the composite
 // (alpha >= 1/255, T < 1e-4, z >= near) agree between the GPU and the CPU oracle, except within a few ulps of a
-// threshold: the rasterizer's pair evaluation uses the hardware v_exp_f32 / v_rcp_f32 (raster.hip eval_hit,
+// threshold: the rasterizer's pair evaluation uses the hardware v_exp_f32 / v_rcp_f32 (raster_common.h eval_hit,
 // GSTEX_FAST_EVAL), and the tests tell such flips apart by the oracle's decision margins.
 //
 // Semantics follow the call-site contracts of the reference (nerfstudio/models/gstex.py) and the
@@ -337,7 +337,7 @@ __device__ __forceinline__ void affine_homog_vjp(V3<T> Tu, V3<T> Tv, V3<T> Tw, V
 
 // Raster record layout (GSTEX_REC_FLOATS = 32 floats = 128 B, one cache line), as 8 float4 planes.
 enum RecField {
-    // dwords [0, 12) (planes 0-2): everything the per-wave cull reads (raster.hip wave_may_hit), so a candidate costs
+    // dwords [0, 12) (planes 0-2): everything the per-wave cull reads (raster_common.h wave_may_hit), so a candidate costs
     // three 16-B loads; every field the photometric backward reads lies in [0, 27) (one contiguous scalar load run
     // per visit)
     R_A = 0, R_B = 3, R_PZ = 6, R_XA = 7, R_YA = 8, R_XY = 9, R_OPAC = 11,

@@ -11,7 +11,7 @@
 //
 // gstex_raster_viewmat_bwd runs after gstex_raster_setup_bwd on the same buffers: the per-splat sums are still in
 // `partials` (accumulator mode: row g; deterministic mode: written over the splat's first row).  It repeats the chain
-// of setup_bwd_chain (raster.hip) as far as the camera-space stage, in fp64, one thread per splat, and reduces the 12
+// of setup_bwd_chain (raster_chain.h) as far as the camera-space stage, in fp64, one thread per splat, and reduces the 12
 // values in two deterministic stages: each 256-thread block reduces in fp64 (wave butterfly, then LDS, fixed order)
 // into its workspace row; one final block sums the rows in a fixed order.  No atomics: two calls on the same inputs
 // give the same bits.

@@ -5,19 +5,39 @@
 //   GSTEX_STATW(i, v)  the same from the first active lane (divergent code)
 //   GSTEX_WG_STAMP(depth, wl)  GSTEX_STATS == 3: per-workgroup timeline (start / end s_memrealtime, tile depth, last
 //                              contributor) for the first 65536 workgroups
+// Included by raster_fwd.hip (which defines GSTEX_DIAG_FWD first) and raster_bwd.hip (GSTEX_DIAG_BWD).  A device global
+// belongs to one unit's code object, so each unit counts into its own g_stats (the slots it does not use stay zero):
+// [0, 8) and [13, 16) backward, [8, 13) forward.  The backward unit owns the gstex_debug_* entry points; its
+// gstex_debug_stats adds the forward's array, fetched through gstex::raster_fwd_debug_stats (gstex_internal.h).
 #pragma once
 #ifndef GSTEX_STATS
 #define GSTEX_STATS 0
 #endif
 #if GSTEX_STATS
-__device__ unsigned long long g_stats[24];  // [0, 8) backward, [8, 13) forward counters, [13, 16) backward
-extern "C" int gstex_debug_stats(unsigned long long* out) {
+namespace {
+constexpr int kDiagStats = 24;
+__device__ unsigned long long g_stats[kDiagStats];  // this unit's counters
+}  // namespace
+#ifdef GSTEX_DIAG_FWD
+namespace gstex {
+int raster_fwd_debug_stats(unsigned long long* out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stats), sizeof(g_stats)) == hipSuccess ? 0 : 2;
+}
+}  // namespace gstex
+#endif
+#ifdef GSTEX_DIAG_BWD
+extern "C" int gstex_debug_stats(unsigned long long* out) {
+    unsigned long long fwd[kDiagStats];
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stats), sizeof(g_stats)) != hipSuccess) return 2;
+    if (gstex::raster_fwd_debug_stats(fwd)) return 2;
+    for (int i = 0; i < kDiagStats; ++i) out[i] += fwd[i];
+    return 0;
 }
 __device__ unsigned long long g_wg[65536 * 4];
 extern "C" int gstex_debug_wg(unsigned long long* out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wg), sizeof(g_wg)) == hipSuccess ? 0 : 2;
 }
+#endif
 #endif
 #if GSTEX_STATS == 1
 #define GSTEX_STAT(i, v) do { const unsigned long long v_ = (v); if ((threadIdx.x & 63) == 0) atomicAdd(&g_stats[i], v_); } while (0)
@@ -27,7 +47,7 @@ extern "C" int gstex_debug_wg(unsigned long long* out) {
 #define GSTEX_STAT(i, v) do { } while (0)
 #define GSTEX_STATW(i, v) do { } while (0)
 #endif
-#if GSTEX_STATS == 3
+#if GSTEX_STATS == 3 && defined(GSTEX_DIAG_BWD)
 struct GstexWgStamp {
     unsigned long long t0;
     int depth, wl;
@@ -47,7 +67,7 @@ struct GstexWgStamp {
 // GSTEX_PAIR_DUMP (tools/hp_pairs.py): every contributing pair of the backward appends one 16-float record
 //   gid (bits), px, py, flags (use3 | aclamp << 1, bits), T, w, dL/dalpha, drho, u, v, 1 / p.z, z, alpha, G, dx, dy
 // to the buffer gstex_debug_pair_dump installed (vector atomics on the count; records past `cap` are dropped).
-#ifdef GSTEX_PAIR_DUMP
+#if defined(GSTEX_PAIR_DUMP) && defined(GSTEX_DIAG_BWD)
 __device__ float* g_pair_buf;
 __device__ int* g_pair_count;
 __device__ int g_pair_cap;

@@ -113,7 +113,7 @@ __device__ __forceinline__ Preprocessed preprocess_splat(const Camera& cam, f3 m
     return p;
 }
 
-// ---- the splat's raster record (raster.hip setup_kernel, gstex_raster_setup) ---------------------------------------
+// ---- the splat's raster record (raster_fwd.hip setup_kernel, gstex_raster_setup) ---------------------------------------
 // Evaluated in fp64 and rounded once per value (one thread per splat, ~100 fp64 operations): its fp32 evaluation was
 // the dominant error of the means / quats gradients (tools/grad_precision.py).  Inputs are the splat's
 // fp32 values (the activated scales / quaternion, its colour, opacity, AABB centre, UV frame and texel block dims).

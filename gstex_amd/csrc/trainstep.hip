@@ -1,5 +1,5 @@
 // trainstep.hip — the launches a photometric training render makes before its raster forward, as one host call
-// (gstex_train_prologue, ABI 17; gstex_amd.fused).
+// (gstex_train_prologue, ABI 17; gstex_amd.fused).  Its counterpart after the raster backward: trainstep_epilogue.hip.
 //
 // Per-op sequence (gstex_amd's per-op path): activate_fwd, preprocess, sh_rest_fwd (one thread per splat each), the
 // guarded offsets scan (three launches: block sums, scan of the sums, final), raster_setup, bin_sort_capped.  Here:

@@ -1,6 +1,6 @@
 """CPU restatement of the textured-2DGS rasterizer (TEST INFRASTRUCTURE ONLY — see oracle/__init__.py).
 
-Follows, op for op in fp32, the device functions of gstex_amd/csrc/gstex_common.h, raster.hip,
+Follows, op for op in fp32, the device functions of gstex_amd/csrc/gstex_common.h, raster_common.h, raster_fwd.hip, raster_edit.hip,
 preprocess.hip and binning.hip, which in turn implement the call-site contracts of
 nerfstudio/models/gstex.py:1059-1170.
 
@@ -65,7 +65,7 @@ def _div(a, b):
 
 
 def _fma(a, b, c):
-    """fp32 fused multiply-add (a * b + c, one rounding) as raster.hip's __builtin_fmaf: the fp64 product is exact
+    """fp32 fused multiply-add (a * b + c, one rounding) as raster_common.h's __builtin_fmaf: the fp64 product is exact
     and the fp64 sum's own rounding can change the fp32 result only at a rounding midpoint (p < 2^-28)."""
     if isinstance(a, torch.Tensor) and a.dtype == F32:
         return (a.double() * b.double() + (c.double() if isinstance(c, torch.Tensor) else float(c))).float()
@@ -304,12 +304,12 @@ class RasterInputs:
     settings: int = SETTING_AA_BLUR | SETTING_DIST_REG
     background: torch.Tensor | None = None  # (3,)
     # near-edge-on splats (|normal . view direction| < K_HP_COS) evaluated with their homogeneous point p from the
-    # fp64 record (raster.hip hit_p_hp, gstex_raster_setup's hp_records): what texture_gaussians does; texture_edit
+    # fp64 record (raster_common.h hit_p_hp, gstex_raster_setup's hp_records): what texture_gaussians does; texture_edit
     # (records without hp rows) does not
     hp: bool = True
 
 
-# raster.hip setup_kernel evaluates the per-splat record in fp64 and rounds each value to fp32 once (and
+# raster_fwd.hip setup_kernel evaluates the per-splat record in fp64 and rounds each value to fp32 once (and
 # setup_bwd_chain differentiates it in fp64): the fp32 evaluation of the record was measured to dominate the
 # means / quats gradient error (tools/grad_precision.py).  False restores the all-fp32 record
 # (precision analysis only).
@@ -345,7 +345,7 @@ class _HpPoint(torch.autograd.Function):
 
 
 def _splat_table(inp: RasterInputs, dtype):
-    """gstex_amd/csrc/raster.hip:setup_kernel — per-splat record in `dtype` (fp32: fp64 evaluation, rounded once)."""
+    """gstex_amd/csrc/raster_fwd.hip:setup_kernel — per-splat record in `dtype` (fp32: fp64 evaluation, rounded once)."""
     if dtype == F32 and RECORD_FP64:
         return {k: (v.to(F32) if v.is_floating_point() else v) for k, v in _splat_table(inp, F64).items()}
     V, campos, fx, fy, cx, cy = inp.cam.cast(dtype)
@@ -362,7 +362,7 @@ def _splat_table(inp: RasterInputs, dtype):
         hp = _dot3(tw, dirv).abs() < K_HP_COS * torch.sqrt(_dot3(dirv, dirv))
     um = inp.umap[:, 0, :].to(dtype).detach()
     vm = inp.vmap[:, 0, :].to(dtype).detach()
-    # the texture affine prescaled to texel units (raster.hip setup_kernel): the sample point (tu h, tv w)
+    # the texture affine prescaled to texel units (raster_fwd.hip setup_kernel): the sample point (tu h, tv w)
     hd = inp.texture_dims[:, 0].to(dtype)
     wd = inp.texture_dims[:, 1].to(dtype)
     # affine form of the homography (gstex_common.h affine_homog): p = dx A + dy B + (0, 0, Pz)
@@ -388,7 +388,7 @@ def rasterize(inp: RasterInputs, grad_dtype=F64, bins=None, table_dtype=None):
     the GPU must reproduce, outputs_hi the `grad_dtype` re-evaluation (differentiable w.r.t. the
     leaf tensors of `inp` that require grad) that shares the fp32 decisions.
     table_dtype (precision analysis, tools/grad_precision.py): evaluate the per-splat table (the chain that
-    raster.hip's setup / setup_bwd implement) in this dtype and only the per-pair part in grad_dtype."""
+    raster_fwd.hip's setup and raster_chain.h's setup_bwd implement) in this dtype and only the per-pair part in grad_dtype."""
     cam = inp.cam
     H, W = cam.H, cam.W
     if bins is None:
@@ -462,12 +462,12 @@ def _render(inp: RasterInputs, dtype, tile_ranges, sorted_ids, decisions, edit=N
         A, B, Tw = g["A"][:, None, :], g["B"][:, None, :], g["Tw"][:, None, :]
         ddx = px - g["xa"][:, None]
         ddy = py - g["ya"][:, None]
-        # p = k x l in the affine form of raster.hip eval_hit: dx A + dy B + (0, 0, Pz), its fused multiply-adds
+        # p = k x l in the affine form of raster_common.h eval_hit: dx A + dy B + (0, 0, Pz), its fused multiply-adds
         pxc = _fma(ddx, A[..., 0], ddy * B[..., 0])
         pyc = _fma(ddx, A[..., 1], ddy * B[..., 1])
         pzc = _fma(ddy, B[..., 2], _fma(ddx, A[..., 2], g["Pz"][:, None]))
         if tab64 is not None and bool(tab64["hp"][ids].any()):
-            # raster.hip hit_p_hp: dx, dy and p of a near-edge-on splat's pairs from its fp64 record, rounded once
+            # raster_common.h hit_p_hp: dx, dy and p of a near-edge-on splat's pairs from its fp64 record, rounded once
             hm = tab64["hp"][ids][:, None]
             x64 = tab64["xa"][ids][:, None]
             y64 = tab64["ya"][ids][:, None]
@@ -501,7 +501,7 @@ def _render(inp: RasterInputs, dtype, tile_ranges, sorted_ids, decisions, edit=N
             d = decisions["tiles"][t]
             nz = d["nz"]
         pzs = torch.where(nz, pzc, torch.ones_like(pzc))
-        ipz = _div(_c(1.0, dtype), pzs)  # raster.hip eval_hit: one reciprocal, two products
+        ipz = _div(_c(1.0, dtype), pzs)  # raster_common.h eval_hit: one reciprocal, two products
         u = pxc * ipz
         v = pyc * ipz
         rho3 = _fma(u, u, v * v)
@@ -530,7 +530,7 @@ def _render(inp: RasterInputs, dtype, tile_ranges, sorted_ids, decisions, edit=N
             # decision margins (test support): the relative distance of every threshold test the GPU repeats in
             # fp32 (alpha >= 1/255, z >= near, T (1 - alpha) < 1e-4, rho3 <= rho2) from its threshold, over the
             # pairs the traversal reaches.  The GPU evaluates exp and 1 / p.z with the hardware v_exp_f32 /
-            # v_rcp_f32 (raster.hip eval_hit), a few ulps from this restatement, so alpha can differ by ~5e-7
+            # v_rcp_f32 (raster_common.h eval_hit), a few ulps from this restatement, so alpha can differ by ~5e-7
             # relative and 1 - alpha by alpha / (1 - alpha) times that: the termination margin is measured in
             # those units
             big = torch.full_like(alpha, float("inf"))
@@ -556,7 +556,7 @@ def _render(inp: RasterInputs, dtype, tile_ranges, sorted_ids, decisions, edit=N
         w_ = tdims[ids, 1][:, None]
         off = tdims[ids, 2][:, None]
         has_tex = (h_ * w_) > 0
-        # raster.hip tex_coords: the sample point in texel units from the prescaled affine
+        # raster_common.h tex_coords: the sample point in texel units from the prescaled affine
         xr = _fma(u, g["auu"][:, None], _fma(v, g["auv"][:, None], g["tu0"][:, None]))
         yr = _fma(u, g["avu"][:, None], _fma(v, g["avv"][:, None], g["tv0"][:, None]))
         hf = h_.to(dtype)
@@ -613,7 +613,7 @@ def _render(inp: RasterInputs, dtype, tile_ranges, sorted_ids, decisions, edit=N
             reg = torch.zeros(P, dtype=dtype)
             M1 = torch.zeros(P, dtype=dtype)
             M2 = torch.zeros(P, dtype=dtype)
-        if edit is not None:  # texture_edit (raster.hip texture_edit_kernel): fp32 per-pair products, fp64 sums
+        if edit is not None:  # texture_edit (raster_edit.hip texture_edit_kernel): fp32 per-pair products, fp64 sums
             pid = torch.from_numpy(pyi * W + pxi)
             erg = edit["rgb"].reshape(-1, 3)[pid].to(dtype)
             ea = edit["a"].reshape(-1)[pid].to(dtype)
@@ -656,7 +656,7 @@ def _render(inp: RasterInputs, dtype, tile_ranges, sorted_ids, decisions, edit=N
             return x.reshape(H, W, width) if width else x.reshape(H, W)
 
         normal = assemble("normal", 3)
-        if inp.settings & SETTING_EVAL_NORMAL:  # raster.hip raster_fwd_kernel: unit normal, 0 where none accumulated
+        if inp.settings & SETTING_EVAL_NORMAL:  # raster_fwd.hip raster_fwd_kernel: unit normal, 0 where none accumulated
             n2 = (normal[..., 0] * normal[..., 0] + normal[..., 1] * normal[..., 1]) + normal[..., 2] * normal[..., 2]
             inv = torch.where(n2 > 0, _div(_c(1.0, n2.dtype), _sqrt(torch.where(n2 > 0, n2, torch.ones_like(n2)))),
                               torch.zeros_like(n2))
@@ -677,7 +677,7 @@ def _render(inp: RasterInputs, dtype, tile_ranges, sorted_ids, decisions, edit=N
 
 
 def texture_edit(inp: RasterInputs, edit_rgb, edit_alpha, depth_lo, depth_hi, bins=None):
-    """raster.hip:texture_edit_kernel (gstex.py:579-606).  The fp32 decision pass of the forward
+    """raster_edit.hip:texture_edit_kernel (gstex.py:579-606).  The fp32 decision pass of the forward
     (same inclusion, weights w = alpha * T, hit depth, texel cell) with the stroke scattered to the
     texels: out[texel] += b * w * (a*rgb, a, 1) for pairs with depth_lo <= z <= depth_hi.  Per-pair
     products in fp32 (the kernel's operation order), sums in fp64; returns (T, 5) float64."""

@@ -224,7 +224,7 @@ def check_stress(name, case, aux):
 
 
 # Channel counts without an instantiation of their own (every C but 3 and 6 runs the raster kernels' runtime-channel
-# build, raster.hip: CM = 8 register slots, Cn = the call's C), at C > 1 so that a wrong channel stride moves an address:
+# build, raster_fwd.hip / raster_bwd.hip: CM = 8 register slots, Cn = the call's C), at C > 1 so that a wrong channel stride moves an address:
 # C = 8 (every slot live), a C = 8 case with texel blocks on both sides of the backward's staging size, an odd C on a
 # ragged image, C = 2, C = 4 without the AA branch, C = 7 with a background.  Fixed inputs; check_channels asserts, from
 # the oracle's run alone, that each reaches its regime.  Seeds tried: the ones below only.
@@ -246,8 +246,8 @@ DEEP_CHANNEL_CASES = {
     "deep_tex8": dict(n=1500, n_texels=15000, H=32, W=32, seed=19, C=8, opacity=0.05),
     "deep_tex5": dict(n=1500, n_texels=15000, H=32, W=32, seed=21, C=5, opacity=0.05),
 }
-TEX_STAGE = 1024  # the backward's texel staging size in entries (raster.hip: kTexStage, GSTEX_TEX_STAGE's default)
-SEG_LEN = 256  # tile-list positions per checkpoint segment (raster.hip: kSegLen, GSTEX_SEG_LEN's default)
+TEX_STAGE = 1024  # the backward's texel staging size in entries (raster_bwd.hip: kTexStage, GSTEX_TEX_STAGE's default)
+SEG_LEN = 256  # tile-list positions per checkpoint segment (raster_common.h: kSegLen, GSTEX_SEG_LEN's default)
 
 
 def check_channels(name, case, aux):

@@ -250,3 +250,109 @@ def test_train_prologue_rejects_null_args(lib):
     assert rc != 0 and "null" in msg
     rc, msg = _status(lib, "gstex_train_epilogue", None, None)
     assert rc != 0 and "invalid" in msg
+
+
+# ---- the four tile-walking raster entry points' argument checks ------------------------------------------------------
+_BUF = (ctypes.c_float * 8)()  # stands for every required device pointer: null-checked only, never read before a launch
+
+
+def _raster_entry_call(lib, entry, H=32, block=16, channels=3, settings=0, n_texels=0, n_isect=0, null=()):
+    """One call of `entry` whose arguments are valid except for the given faults (`null`: required pointers passed
+    as NULL).  Every case of the table below has a fault, so the call returns before any HIP call."""
+    p = ctypes.addressof(_BUF)
+    cam = _cam(H=H, block=block)
+
+    def ptrs(*names):
+        return {n: (None if n in null else p) for n in names}
+
+    if entry in ("gstex_raster_fwd", "gstex_raster_bwd"):
+        scene = _lib.GstexRasterScene(cam=cam, channels=channels, settings=settings, tex_scale=1.0, n_texels=n_texels,
+                                      n_isect=n_isect, **ptrs("records", "tile_ranges", "sorted_ids", "texture", "state", "aux"))
+        if entry == "gstex_raster_fwd":
+            args = _lib.GstexRasterFwdArgs(scene=scene, **ptrs("out_img", "out_alpha", "out_tex"))
+        else:
+            args = _lib.GstexRasterBwdArgs(scene=scene, **ptrs("sorted_slots", "v_img", "v_alpha", "v_tex",
+                                                               "partials", "v_texture"))
+        return _status(lib, entry, ctypes.byref(args), None)
+    if entry == "gstex_texture_edit":
+        q = ptrs("records", "tile_ranges", "sorted_ids", "edit_rgb", "edit_alpha", "depth_lo", "depth_hi", "out")
+        return _status(lib, entry, ctypes.byref(cam), settings, q["records"], q["tile_ranges"], None,
+                       q["sorted_ids"], q["edit_rgb"], q["edit_alpha"], q["depth_lo"], q["depth_hi"], n_texels,
+                       q["out"], None)
+    assert entry == "gstex_paint_scatter"
+    args = _lib.GstexPaintScatterArgs(cam=cam, settings=settings, stroke_dtype=_lib.GT_F32, eps=0.01,
+                                      n_texels=n_texels,
+                                      **ptrs("records", "tile_ranges", "sorted_ids", "stroke", "depth", "acc"))
+    return _status(lib, entry, ctypes.byref(args), None)
+
+
+_FWD, _BWD, _EDIT, _PAINT = "gstex_raster_fwd", "gstex_raster_bwd", "gstex_texture_edit", "gstex_paint_scatter"
+_REQUIRED = {_FWD: "out_img", _BWD: "aux", _EDIT: "edit_rgb", _PAINT: "depth"}  # the pointer the null cases drop
+_GAUSS_SETTINGS = "texture_gaussians: unsupported settings bits 0x%x (supported: 1<<9, 1<<10, 1<<15)"
+# (entry point, faults, status, message): status and message as the library gave them before the entry checks were
+# shared (the message must still contain that text).  The cases from `block=8, channels=9` on break two rules each and
+# pin which one is reported: every entry point keeps its own order of checks.
+_RASTER_REJECTIONS = [
+    (_FWD, dict(H=0), 1, "gstex_raster_fwd: invalid camera"),
+    (_BWD, dict(H=0), 1, "gstex_raster_bwd: invalid camera"),
+    (_EDIT, dict(H=0), 1, "gstex_texture_edit: invalid camera"),
+    (_PAINT, dict(H=0), 1, "gstex_paint_scatter: invalid camera"),
+    (_FWD, dict(block=8), 1, "gstex_raster_fwd: block_width must be 16 (got 8)"),
+    (_BWD, dict(block=8), 1, "gstex_raster_bwd: block_width must be 16"),
+    (_EDIT, dict(block=8), 1, "gstex_texture_edit: block_width must be 16 (got 8)"),
+    (_PAINT, dict(block=8), 1, "gstex_paint_scatter: block_width must be 16 (got 8)"),
+    (_FWD, dict(channels=0), 1, "gstex_raster_fwd: channels must be in [1, 8] (got 0)"),
+    (_FWD, dict(channels=9), 1, "gstex_raster_fwd: channels must be in [1, 8] (got 9)"),
+    (_BWD, dict(channels=0), 1, "gstex_raster_bwd: channels must be in [1, 8]"),
+    (_BWD, dict(channels=9), 1, "gstex_raster_bwd: channels must be in [1, 8]"),
+    (_FWD, dict(settings=1 << 2), 3, _GAUSS_SETTINGS % 4),
+    (_BWD, dict(settings=1 << 2), 3, _GAUSS_SETTINGS % 4),
+    (_EDIT, dict(settings=1 << 2), 3, "texture_edit: unsupported settings bits 0x4"),
+    (_PAINT, dict(settings=1 << 2), 3, "gstex_paint_scatter: unsupported settings bits 0x4"),
+    # bit 13 (GSTEX_SETTING_EDIT): the renders reject it; edit and paint accept it and go on to the pointer check
+    (_FWD, dict(settings=1 << 13), 3, _GAUSS_SETTINGS % 0x2000),
+    (_BWD, dict(settings=1 << 13), 3, _GAUSS_SETTINGS % 0x2000),
+    (_EDIT, dict(settings=1 << 13, null=("tile_ranges",)), 1, "gstex_texture_edit: null pointer"),
+    (_PAINT, dict(settings=1 << 13, null=("tile_ranges",)), 1, "gstex_paint_scatter: null pointer"),
+    (_FWD, dict(n_texels=-1), 1, "gstex_raster_fwd: n_texels out of range"),
+    (_BWD, dict(n_texels=-1), 1, "gstex_raster_bwd: n_texels out of range"),
+    (_EDIT, dict(n_texels=-1), 1, "gstex_texture_edit: n_texels < 0"),
+    (_PAINT, dict(n_texels=-1), 1, "gstex_paint_scatter: n_texels out of range (-1)"),
+    (_FWD, dict(n_isect=-1), 1, "gstex_raster_fwd: n_isect out of range"),
+    (_BWD, dict(n_isect=-1), 1, "gstex_raster_bwd: n_isect out of range"),
+    (_FWD, dict(null=(_REQUIRED[_FWD],)), 1, "gstex_raster_fwd: null pointer"),
+    (_BWD, dict(null=(_REQUIRED[_BWD],)), 1, "gstex_raster_bwd: null pointer (tile_ranges, state and the forward's aux)"),
+    (_EDIT, dict(null=(_REQUIRED[_EDIT],)), 1, "gstex_texture_edit: null pointer"),
+    (_PAINT, dict(null=(_REQUIRED[_PAINT],)), 1, "gstex_paint_scatter: null pointer"),
+    (_FWD, dict(block=8, channels=9), 1, "gstex_raster_fwd: block_width must be 16 (got 8)"),
+    (_BWD, dict(block=8, channels=9), 1, "gstex_raster_bwd: block_width must be 16"),
+    (_FWD, dict(settings=1 << 2, null=(_REQUIRED[_FWD],)), 3, _GAUSS_SETTINGS % 4),
+    (_BWD, dict(settings=1 << 2, null=(_REQUIRED[_BWD],)), 3, _GAUSS_SETTINGS % 4),
+    (_EDIT, dict(settings=1 << 2, null=(_REQUIRED[_EDIT],)), 3, "texture_edit: unsupported settings bits 0x4"),
+    (_PAINT, dict(settings=1 << 2, null=(_REQUIRED[_PAINT],)), 3, "gstex_paint_scatter: unsupported settings bits 0x4"),
+    # the settings against the ranges: only the forward checks n_texels (and its texture) ahead of the settings
+    (_FWD, dict(settings=1 << 2, n_texels=-1), 1, "gstex_raster_fwd: n_texels out of range"),
+    (_BWD, dict(settings=1 << 2, n_texels=-1), 3, _GAUSS_SETTINGS % 4),
+    (_EDIT, dict(settings=1 << 2, n_texels=-1), 3, "texture_edit: unsupported settings bits 0x4"),
+    (_PAINT, dict(settings=1 << 2, n_texels=-1), 3, "gstex_paint_scatter: unsupported settings bits 0x4"),
+    (_FWD, dict(settings=1 << 2, n_isect=-1), 3, _GAUSS_SETTINGS % 4),
+    (_BWD, dict(settings=1 << 2, n_isect=-1), 3, _GAUSS_SETTINGS % 4),
+    (_FWD, dict(settings=1 << 2, n_texels=1, null=("texture",)), 1, "gstex_raster_fwd: null texture"),
+    (_BWD, dict(settings=1 << 2, n_texels=1, null=("texture",)), 3, _GAUSS_SETTINGS % 4),
+    # the required pointers come before n_isect; the channels before n_texels; n_texels and n_isect either way round
+    (_FWD, dict(n_isect=-1, null=(_REQUIRED[_FWD],)), 1, "gstex_raster_fwd: null pointer"),
+    (_BWD, dict(n_isect=-1, null=(_REQUIRED[_BWD],)), 1, "gstex_raster_bwd: null pointer (tile_ranges, state and the forward's aux)"),
+    (_FWD, dict(channels=9, n_texels=-1), 1, "gstex_raster_fwd: channels must be in [1, 8] (got 9)"),
+    (_BWD, dict(channels=9, n_texels=-1), 1, "gstex_raster_bwd: channels must be in [1, 8]"),
+    (_FWD, dict(n_texels=-1, n_isect=-1), 1, "gstex_raster_fwd: n_texels out of range"),
+    (_BWD, dict(n_texels=-1, n_isect=-1), 1, "gstex_raster_bwd: n_isect out of range"),
+    (_BWD, dict(n_texels=1, null=("v_texture",)), 1, "gstex_raster_bwd: null texture"),
+    # gstex_texture_edit puts no upper bound on n_texels: the call goes on to its pointer check
+    (_EDIT, dict(n_texels=2**31 - 1, null=("tile_ranges",)), 1, "gstex_texture_edit: null pointer"),
+]
+
+
+def test_raster_entry_rejections(lib):
+    for entry, faults, status, text in _RASTER_REJECTIONS:
+        rc, msg = _raster_entry_call(lib, entry, **faults)
+        assert rc == status and text in msg, (entry, faults, rc, msg)

@@ -18,7 +18,7 @@ from oracle import raster as O
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-TEX_STAGE_TEXELS = 341  # raster.hip kTexStage / 3: a larger block's run tails go straight to global memory
+TEX_STAGE_TEXELS = 341  # raster_bwd.hip kTexStage / 3: a larger block's run tails go straight to global memory
 DEEP_SCALE = 16.0  # the deep-list scene's splat enlargement (median screen extent 11 px; the other scenes' is 15)
 
 

@@ -4,7 +4,7 @@ Tolerances (written here, per north_star): integer/index work bit-exact; forward
 1e-5 abs + 1e-5 rel of the oracle's fp64 evaluation (same fp32 decisions).  Gradients, against
 the oracle's fp64 autograd of the same function:
   * norm-wise relative error ||g - ref|| / ||ref|| and element-wise max|g - ref| / max|ref| are each
-    <= 1e-5, outright.  The raster record is evaluated in fp64 and rounded once (raster.hip setup_kernel;
+    <= 1e-5, outright.  The raster record is evaluated in fp64 and rounded once (raster_fwd.hip setup_kernel;
     setup_bwd_chain in fp64), and near-edge-on splats (|normal . view dir| < 0.1, whose p = dx A + dy B + (0, 0, Pz)
     is a small difference of larger terms) take p from their fp64 setup row in the forward and the backward alike
     (DESIGN.md §4); the oracle restates both (RasterInputs.hp) and evaluates with the fp32-rounded camera

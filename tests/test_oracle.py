@@ -255,7 +255,7 @@ def test_texture_edit_uniform_stroke_known_answer():
 
 
 def test_near_edge_on_rows_change_only_the_ill_conditioned_pairs():
-    """RasterInputs.hp (raster.hip hit_p_hp: near-edge-on splats' p from their fp64 row, rounded once): the fp32 pass
+    """RasterInputs.hp (raster_common.h hit_p_hp: near-edge-on splats' p from their fp64 row, rounded once): the fp32 pass
     moves by fp32 noise only (the fp64 evaluation is the same function), and only pixels of marked splats move."""
     import sys
     sys.path.insert(0, __file__.rsplit("/", 1)[0])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""CPU emulation of raster.hip's backward recurrences, to locate the means / quats error of the HIP backward on
+"""CPU emulation of raster_bwd.hip's backward recurrences, to locate the means / quats error of the HIP backward on
 near-edge-on splats (precision analysis, test infrastructure: imports oracle/).  The oracle's fp32 gradient pass
 supplies every pair's fp32 values (u, v, 1/p.z, rho branch, depth, G, alpha, decisions) and every pixel's final state;
 the emulation then walks each pixel's list back to front exactly as raster_bwd_kernel does (T recovered by division,
@@ -144,7 +144,7 @@ def chain(case, sums, leaves, tab, knobs):
     if "s32" in knobs:  # the GPU's per-splat sums are fp32
         sums = {k: v.float().double() for k, v in sums.items()}
     if "anch" in knobs:
-        # raster.hip setup_bwd_chain: the anchored vjp (anchor held fixed, the zero-valued z components of Tu', Tv'
+        # raster_chain.h setup_bwd_chain: the anchored vjp (anchor held fixed, the zero-valued z components of Tu', Tv'
         # carry gradient), fp64
         V, campos, fx, fy, cx, cy = inp.cam.cast(F64)
         tu, tv, tw = O.quat_frame(leaves["quats"].to(F64))

@@ -3,15 +3,15 @@
 
 Runs the CPU oracle's autograd on a window of a bench scene in three precision mixes and reports each
 gradient's norm-wise and max relative error against the all-fp64 evaluation:
-  fp32        per-splat table (the chain raster.hip's setup / setup_bwd implement) and per-pair part in fp32
+  fp32        per-splat table (the chain raster_fwd.hip's setup and raster_chain.h's setup_bwd implement) and per-pair part in fp32
               (--fp32-record: the round-2 formulation; default: the record evaluated in fp64 and rounded once, the
-              current raster.hip setup_kernel / setup_bwd_chain) -- its error is the tests' "fp32 floor";
+              current raster_fwd.hip setup_kernel / raster_chain.h setup_bwd_chain) -- its error is the tests' "fp32 floor";
   pair32      table fp64, per-pair fp32 (a GPU whose setup_bwd chain ran in fp64);
   table32     table fp32, per-pair fp64;
 With the fp64 record (default) "table32" means the fp64 record rounded to fp32, so pair64/table32 isolates the
 rounding of the stored record: exact arithmetic everywhere else -- the conditioning floor of an fp32 record.
   fp32+hp     the build: fp32, with the near-edge-on splats' (|normal . view| < 0.1) homogeneous point p evaluated from
-              their fp64 record (raster.hip hit_p_hp; the oracle's RasterInputs.hp)
+              their fp64 record (raster_common.h hit_p_hp; the oracle's RasterInputs.hp)
   hp<c        --hp-cos c: as pair64/table32, but the table of the near-edge-on splats (|normal . view| < c) kept fp64
 Test infrastructure only (imports oracle/).  Usage: python tools/grad_precision.py [--win 48] [--cfg 3] [--hp-cos 0.05]
 """
@@ -52,7 +52,7 @@ GRAD32 = False  # --grad32: the table's gradient (the per-splat sums the GPU red
 
 
 def hp_mask_table(case, thr):
-    """Precision analysis of raster.hip's near-edge-on path (GSTEX_HP_COS): in the gradient pass, the per-splat table of
+    """Precision analysis of the raster kernels' near-edge-on path (GSTEX_HP_COS): in the gradient pass, the per-splat table of
     the splats with |normal . view direction| < thr stays fp64 while the others are rounded to fp32 -- what
     gstex_raster_setup_hp / gstex_raster_bwd_hp do (fp64 dx, dy, 1 / p.z, u, v for those splats).  Returns a restore
     function (patches the oracle; decisions stay the fp32 pass's)."""
@@ -99,7 +99,7 @@ def main():
                     help="a tests/test_gpu_parity.py CASES entry, or cfg1 (tests/test_gpu_deep.py), instead of a window")
     ap.add_argument("--fp32-record", action="store_true", help="all-fp32 per-splat record (round-2 formulation)")
     ap.add_argument("--hp-cos", type=float, nargs="*", default=[],
-                    help="also: the table of splats with |normal . view dir| < each value kept fp64 (raster.hip GSTEX_HP_COS)")
+                    help="also: the table of splats with |normal . view dir| < each value kept fp64 (gstex_common.h GSTEX_HP_COS)")
     ap.add_argument("--grad32", action="store_true",
                     help="with --hp-cos: the per-splat table gradient rounded to fp32 (the GPU's fp32 sums)")
     ap.add_argument("--hp-sum32", action="store_true",
@@ -129,7 +129,7 @@ def main():
         for k in DIFF:
             cells.append(f"{grad_norm_err(g[k], ref[k]):.2e}/{grad_rel_err(g[k], ref[k])[0]:.2e}")
         print(f"{name:16s} " + " ".join(f"{c:>18s}" for c in cells))
-    # the build: fp32, with the near-edge-on splats' homogeneous point from their fp64 record (raster.hip hit_p_hp)
+    # the build: fp32, with the near-edge-on splats' homogeneous point from their fp64 record (raster_common.h hit_p_hp)
     case.inp.hp = True
     g = grads(case, F32, F32, outputs)
     frac = float(O._splat_table(case.inp, F64)["hp"].double().mean())

@@ -4,7 +4,7 @@
 from the fp64 record, as the HIP kernels) hands over every pair's dL/dp; the per-splat sums dL/dA = sum dp dx,
 dL/dB = sum dp dy, dL/dPz = sum dp.z are then formed
   exact   in fp64 with the fp64 offsets,
-  gpu     as raster.hip does: fp32 products, fp32 sums per 8x8 quadrant (one backward visit), fp32 accumulation of the
+  gpu     as raster_bwd.hip does: fp32 products, fp32 sums per 8x8 quadrant (one backward visit), fp32 accumulation of the
           visits (the per-splat float atomics),
   and the variants named on the command line,
 and each is pushed through the same fp64 chain (autograd of the fp64 record); the printed error is relative to the
