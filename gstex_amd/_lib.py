@@ -171,6 +171,34 @@ class GstexDensityApplyArgs(ctypes.Structure):
         ("tensors", POINTER(GstexDensityTensor))]
 
 
+class GstexTsdfVolume(ctypes.Structure):
+    """gstex_tsdf_volume (added within ABI 19): the dense grid of the mesh-extraction entry points."""
+    _fields_ = [("nx", c_int32), ("ny", c_int32), ("nz", c_int32), ("origin", c_float * 3), ("voxel_size", c_float),
+                ("tsdf", c_void_p), ("weight", c_void_p), ("color", c_void_p)]
+
+
+class GstexTsdfView(ctypes.Structure):
+    """gstex_tsdf_view (added within ABI 19): one view of gstex_tsdf_integrate."""
+    _fields_ = [("cam", GstexCamera), ("depth", c_void_p), ("alpha", c_void_p), ("rgb", c_void_p)]
+
+
+class GstexTsdfIntegrateArgs(ctypes.Structure):
+    """gstex_tsdf_integrate_args (added within ABI 19)."""
+    _fields_ = [("vol", GstexTsdfVolume), ("n_views", c_int32), ("sdf_trunc", c_float), ("alpha_min", c_float),
+                ("depth_trunc", c_float), ("near_z", c_float), ("views", POINTER(GstexTsdfView))]
+
+
+class GstexMeshExtractArgs(ctypes.Structure):
+    """gstex_mesh_extract_args (added within ABI 19): marching tetrahedra's mark and emit passes."""
+    _fields_ = [("vol", GstexTsdfVolume)] + [
+        (name, c_void_p) for name in ("table", "edge_mask", "vertex_count", "face_count", "vertex_offsets",
+                                      "face_offsets")] + [
+        ("n_vertices", c_int64), ("n_faces", c_int64), ("vertices", c_void_p), ("colors", c_void_p),
+        ("faces", c_void_p)]
+
+
+TSDF_MAX_VIEWS = 8  # GSTEX_TSDF_MAX_VIEWS
+MESH_TABLE_WORDS = 102  # GSTEX_MESH_TABLE_WORDS
 DENSITY_KEEP, DENSITY_CLONE, DENSITY_SPLIT, DENSITY_PRUNE = 0, 1, 2, 3  # GSTEX_DENSITY_*
 DENSITY_ROLE_COPY, DENSITY_ROLE_MOMENT, DENSITY_ROLE_MEANS, DENSITY_ROLE_LOG_SCALES = 0, 1, 2, 3  # GSTEX_DENSITY_ROLE_*
 DENSITY_MAX_TENSORS = 24  # GSTEX_DENSITY_MAX_TENSORS
@@ -255,6 +283,9 @@ SIGNATURES = {
     "gstex_density_accum": (c_int32, [c_int32, _P, _P, _CAM, _P, _P, _P, _P, _P, _P, _P]),
     "gstex_density_plan": (c_int32, [POINTER(GstexDensityPlanArgs), _P]),
     "gstex_density_apply": (c_int32, [POINTER(GstexDensityApplyArgs), _P]),
+    "gstex_tsdf_integrate": (c_int32, [POINTER(GstexTsdfIntegrateArgs), _P]),
+    "gstex_mesh_extract_mark": (c_int32, [POINTER(GstexMeshExtractArgs), _P]),
+    "gstex_mesh_extract_emit": (c_int32, [POINTER(GstexMeshExtractArgs), _P]),
 }
 
 _lib = None

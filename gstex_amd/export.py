@@ -102,6 +102,18 @@ def export_2dgs_ply(trainer, path) -> None:
     write_ply(path, {k: np.ascontiguousarray(v) for k, v in cols.items()}, binary=True)
 
 
+def export_mesh_ply(trainer, views, path, **kw):
+    """GStexTrainer.extract_mesh(views, **kw) written as a triangle-mesh PLY (gstex_amd.ply.write_mesh_ply): the
+    lineage's second deliverable next to the checkpoint PLY.  -> (vertices, colors, faces) as extract_mesh returns
+    them."""
+    from .ply import write_mesh_ply
+
+    vertices, colors, faces = trainer.extract_mesh(views, **kw)
+    write_mesh_ply(path, vertices.cpu().numpy(), faces.cpu().numpy(),
+                   None if colors is None else colors.cpu().numpy())
+    return vertices, colors, faces
+
+
 def trainer_from_npz(path, device, **trainer_kwargs):
     """A GStexTrainer holding exactly the exported parameters (fresh optimizer state)."""
     from .model import GStexTrainer

@@ -3,7 +3,8 @@
 ``read_ply`` returns what the reference reads of such a file (``plydata.elements[0][name]``, gstex.py:608-694): the
 scalar properties of the file's FIRST element, one 1-D array per property in the file's own type.  Elements after the
 first (a mesh's ``face`` with its list property, say) are not parsed.  ``write_ply`` writes one element of scalar
-columns, little-endian binary or ascii.
+columns, little-endian binary or ascii.  ``write_mesh_ply`` writes a triangle mesh: a ``vertex`` element and a
+``face`` element with the usual ``vertex_indices`` list.
 
 Sizes come from the header and are checked against the file's length before any array is made; nothing is read past
 the first element's rows.  Every defect is a ``PlyError`` naming the path.
@@ -138,6 +139,46 @@ def read_ply(path) -> dict:
                            f"{len(rows)}")
         return {name: _ascii_column([r[i].decode("ascii", "replace") for r in rows], code, path, name)
                 for i, (name, code) in enumerate(props)}
+
+
+def write_mesh_ply(path, vertices, faces, colors=None) -> None:
+    """A triangle mesh, little-endian binary: a `vertex` element of float x, y, z and, with `colors` (V, 3) in [0, 1],
+    uchar red, green, blue = clamp(c, 0, 1) * 255 truncated; then a `face` element of `property list uchar int
+    vertex_indices`, three indices per face.  read_ply of the file returns the vertex columns."""
+    path = os.fspath(path)
+    v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float32))
+    f = np.ascontiguousarray(np.asarray(faces))
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise PlyError(f"{path}: vertices have shape {v.shape}; expected (V, 3)")
+    if f.size == 0:
+        f = f.reshape(0, 3)
+    if f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+        raise PlyError(f"{path}: faces have shape {f.shape} and dtype {f.dtype}; expected integer (F, 3)")
+    if f.size and (int(f.min()) < 0 or int(f.max()) >= v.shape[0]):
+        raise PlyError(f"{path}: a face index is outside [0, {v.shape[0]})")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if colors is not None:
+        c = np.asarray(colors, dtype=np.float32)
+        if c.shape != v.shape:
+            raise PlyError(f"{path}: colors have shape {c.shape}, vertices {v.shape}")
+        rgb = (np.clip(c, np.float32(0.0), np.float32(1.0)) * np.float32(255.0)).astype(np.uint8)
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    vdata = np.empty(v.shape[0], dtype=fields)
+    for k, name in enumerate("xyz"):
+        vdata[name] = v[:, k]
+    if colors is not None:
+        for k, name in enumerate(("red", "green", "blue")):
+            vdata[name] = rgb[:, k]
+    fdata = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    fdata["n"] = 3
+    fdata["i"] = f
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}"]
+    head += [f"property {_NAMES[code.lstrip('<')]} {name}" for name, code in fields]
+    head += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as out:
+        out.write(("\n".join(head) + "\n").encode("ascii"))
+        vdata.tofile(out)
+        fdata.tofile(out)
 
 
 def write_ply(path, columns, *, binary: bool = True, element: str = "vertex", comments=()) -> None:

@@ -771,6 +771,83 @@ typedef struct gstex_density_apply_args {
 } gstex_density_apply_args;
 int gstex_density_apply(const gstex_density_apply_args* args, void* stream);
 
+/* ---- mesh extraction: TSDF fusion and marching tetrahedra -- added within ABI 19 (additive); not in the reference,
+ * whose lineage leaves it to Open3D (DESIGN.md "Mesh extraction") --------------------------------------------------
+ * The volume is a dense grid (nz, ny, nx), x fastest: sample (i, j, k) sits at origin + voxel_size * (i, j, k) and has
+ * the linear index v = (k * ny + j) * nx + i.  Caller-owned DEVICE arrays: tsdf[n_vox], weight[n_vox] and, nullable,
+ * color[3][n_vox] (three planes); a fresh volume is all zeros.  Every dim must be >= 2 (INVALID_ARG) and 7 * n_vox
+ * below 2^31 (UNSUPPORTED: a vertex is keyed by 7 * v + edge class).  Every value below is computed by individually
+ * rounded fp32 + - * / in the order DESIGN.md states, so gstex_amd.mesh's eager twins reproduce the entry points bit
+ * for bit. */
+typedef struct gstex_tsdf_volume {
+    int32_t nx, ny, nz;
+    float origin[3];
+    float voxel_size;
+    float* tsdf;
+    float* weight;
+    float* color; /* nullable */
+} gstex_tsdf_volume;
+
+#define GSTEX_TSDF_MAX_VIEWS 8
+typedef struct gstex_tsdf_view {
+    gstex_camera cam;   /* viewmat, fx, fy, cx, cy, H, W are read */
+    const float* depth; /* (H, W): the raster's un-normalised depth, sum of w z */
+    const float* alpha; /* (H, W) */
+    const float* rgb;   /* (H, W, 3); nullable when the volume has no colour */
+} gstex_tsdf_view;
+/* gstex_tsdf_integrate: ONE launch fuses n_views (1..GSTEX_TSDF_MAX_VIEWS) views into the volume, one thread per
+ * voxel; the voxel's (tsdf, weight, colour) stays in registers across the views, in view order, and is stored once,
+ * and only if some view changed it.  Per view, with p the voxel's world position and (x, y, z) = viewmat p: skipped
+ * unless z > near_z; u = fx * (x / z) + cx, v = fy * (y / z) + cy; skipped unless 0 <= u < W and 0 <= v < H; pixel
+ * (r, c) = ((int)v, (int)u); a = alpha[r][c], skipped unless a >= alpha_min; d = depth[r][c] / a, skipped unless
+ * d > 0 and (depth_trunc == 0 or d <= depth_trunc); s = d - z, skipped if s < -sdf_trunc; t = min(1, s / sdf_trunc);
+ * tsdf = (tsdf * w + t) / (w + 1), colour alike, w = w + 1.  sdf_trunc, alpha_min and near_z must be > 0,
+ * depth_trunc >= 0 (0 = off). */
+typedef struct gstex_tsdf_integrate_args {
+    gstex_tsdf_volume vol;
+    int32_t n_views;
+    float sdf_trunc;
+    float alpha_min;
+    float depth_trunc;
+    float near_z;
+    const gstex_tsdf_view* views; /* HOST array of n_views entries */
+} gstex_tsdf_integrate_args;
+int gstex_tsdf_integrate(const gstex_tsdf_integrate_args* args, void* stream);
+
+/* Marching tetrahedra on the volume.  The cell with lower corner (i, j, k) (i < nx - 1, ...) is split into the six
+ * Kuhn tetrahedra; a tetrahedron emits only if its four corners have weight > 0, a corner is inside iff tsdf < 0, and
+ * a vertex lies on every edge whose ends differ: owned by the edge's lower corner A (upper corner B, B - A one of the
+ * seven classes (1,0,0) (0,1,0) (0,0,1) (1,1,0) (0,1,1) (1,0,1) (1,1,1)), at pA + t * (pB - pA), t = tA / (tA - tB).
+ * table: DEVICE int32[GSTEX_MESH_TABLE_WORDS], made by gstex_amd.mesh (the twin reads the same words): word
+ * [tet * 16 + case] (case = sum of inside(corner k) << k) holds the triangle count in bits 24..25 and, for slot
+ * s = 3 * triangle + index, the edge's two tetrahedron corners in bits 4s..4s+1 (lower) and 4s+2..4s+3 (upper); word
+ * [96 + tet] holds the tetrahedron's corner k as dx | dy << 1 | dz << 2 in bits 3k..3k+2.
+ *   gstex_mesh_extract_mark  edge_mask[v] = the classes of v's edges that carry a vertex (zeroed here first),
+ *                            then vertex_count[v] = their number and face_count[v] = the faces of cell v (0 for
+ *                            the voxels of the last row, column and slab, which are no cell's lower corner);
+ *   gstex_scan_offsets over vertex_count and face_count (the caller), ONE read-back of the two totals;
+ *   gstex_mesh_extract_emit  vertices (n_vertices, 3), nullable colors (n_vertices, 3) and faces (n_faces, 3):
+ *                            vertices ascend in 7 * v(owner) + class, faces in (cell, tetrahedron, triangle), each
+ *                            face's indices in the table's order.  Nothing is written past n_vertices / n_faces rows.
+ * All work arrays are DEVICE int32 of n_vox (counts, mask) or n_vox + 1 (offsets) entries. */
+#define GSTEX_MESH_TABLE_WORDS 102
+typedef struct gstex_mesh_extract_args {
+    gstex_tsdf_volume vol;
+    const int32_t* table;
+    int32_t* edge_mask;
+    int32_t* vertex_count;
+    int32_t* face_count;
+    const int32_t* vertex_offsets; /* emit only */
+    const int32_t* face_offsets;   /* emit only */
+    int64_t n_vertices;            /* emit only: rows of vertices / colors */
+    int64_t n_faces;               /* emit only: rows of faces */
+    float* vertices;
+    float* colors; /* nullable; needs vol.color */
+    int32_t* faces;
+} gstex_mesh_extract_args;
+int gstex_mesh_extract_mark(const gstex_mesh_extract_args* args, void* stream);
+int gstex_mesh_extract_emit(const gstex_mesh_extract_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
