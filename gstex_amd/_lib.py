@@ -197,7 +197,30 @@ class GstexMeshExtractArgs(ctypes.Structure):
         ("faces", c_void_p)]
 
 
+class GstexNnGrid(ctypes.Structure):
+    """gstex_nn_grid (added within ABI 19): the uniform grid of the nearest-neighbour entry points."""
+    _fields_ = [("origin", c_float * 3), ("cell_size", c_float), ("nx", c_int32), ("ny", c_int32), ("nz", c_int32)]
+
+
+class GstexNnQueryArgs(ctypes.Structure):
+    """gstex_nn_query_args (added within ABI 19)."""
+    _fields_ = [("grid", GstexNnGrid), ("n_points", c_int64), ("cell_start", c_void_p), ("records", c_void_p),
+                ("n_queries", c_int64), ("queries", c_void_p), ("k", c_int32), ("exclude_self", c_int32),
+                ("max_radius", c_float), ("d2", c_void_p), ("index", c_void_p)]
+
+
+class GstexMeshSampleArgs(ctypes.Structure):
+    """gstex_mesh_sample_args (added within ABI 19): the mesh sampler's mark and emit passes."""
+    _fields_ = [("n_vertices", c_int64), ("n_faces", c_int64), ("vertices", c_void_p), ("faces", c_void_p),
+                ("spacing", c_float), ("count", c_void_p), ("stats", c_void_p), ("offsets", c_void_p),
+                ("n_samples", c_int64), ("samples", c_void_p), ("weights", c_void_p), ("face_of", c_void_p)]
+
+
 TSDF_MAX_VIEWS = 8  # GSTEX_TSDF_MAX_VIEWS
+NN_MAX_CELLS = 1 << 26  # GSTEX_NN_MAX_CELLS
+NN_MAX_AXIS_CELLS = 4096  # GSTEX_NN_MAX_AXIS_CELLS
+NN_MAX_K = 8  # GSTEX_NN_MAX_K
+SAMPLE_MAX_N = 256  # GSTEX_SAMPLE_MAX_N
 MESH_TABLE_WORDS = 102  # GSTEX_MESH_TABLE_WORDS
 DENSITY_KEEP, DENSITY_CLONE, DENSITY_SPLIT, DENSITY_PRUNE = 0, 1, 2, 3  # GSTEX_DENSITY_*
 DENSITY_ROLE_COPY, DENSITY_ROLE_MOMENT, DENSITY_ROLE_MEANS, DENSITY_ROLE_LOG_SCALES = 0, 1, 2, 3  # GSTEX_DENSITY_ROLE_*
@@ -286,6 +309,11 @@ SIGNATURES = {
     "gstex_tsdf_integrate": (c_int32, [POINTER(GstexTsdfIntegrateArgs), _P]),
     "gstex_mesh_extract_mark": (c_int32, [POINTER(GstexMeshExtractArgs), _P]),
     "gstex_mesh_extract_emit": (c_int32, [POINTER(GstexMeshExtractArgs), _P]),
+    "gstex_nn_grid_count": (c_int32, [POINTER(GstexNnGrid), c_int64, _P, _P, _P]),
+    "gstex_nn_grid_place": (c_int32, [POINTER(GstexNnGrid), c_int64, _P, _P, _P, _P, _P]),
+    "gstex_nn_query": (c_int32, [POINTER(GstexNnQueryArgs), _P]),
+    "gstex_mesh_sample_mark": (c_int32, [POINTER(GstexMeshSampleArgs), _P]),
+    "gstex_mesh_sample_emit": (c_int32, [POINTER(GstexMeshSampleArgs), _P]),
 }
 
 _lib = None

@@ -114,6 +114,19 @@ def export_mesh_ply(trainer, views, path, **kw):
     return vertices, colors, faces
 
 
+def score_mesh_ply(trainer, views, reference_ply, **kw) -> dict:
+    """GStexTrainer.score_mesh(views, reference, **kw) with the reference point cloud read from a PLY (its x y z
+    columns, gstex_amd.ply.read_ply)."""
+    from .ply import read_ply
+
+    cols = read_ply(reference_ply)
+    missing = [c for c in ("x", "y", "z") if c not in cols]
+    if missing:
+        raise ValueError(f"{reference_ply}: no property {missing[0]!r} (has {', '.join(cols) or 'none'})")
+    ref = np.stack([np.asarray(cols[c], np.float32) for c in ("x", "y", "z")], axis=1)
+    return trainer.score_mesh(views, torch.from_numpy(ref), **kw)
+
+
 def trainer_from_npz(path, device, **trainer_kwargs):
     """A GStexTrainer holding exactly the exported parameters (fresh optimizer state)."""
     from .model import GStexTrainer

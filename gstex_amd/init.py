@@ -131,31 +131,35 @@ def scene_from_2dgs_ply(path, sh_degree: int = 3, fix_init: bool = False) -> Sce
     return _one_texel_scene(means, scales, quats, opacity, features_dc, features_rest)
 
 
-def _seeded_scene(means, features_dc, sh_degree, log_scales=None, quats=None, opacity=None, seed=42) -> Scene:
+def _seeded_scene(means, features_dc, sh_degree, log_scales=None, quats=None, opacity=None, seed=42,
+                  knn_device=None) -> Scene:
     n = means.shape[0]
     features_rest = torch.zeros((n, (sh_degree + 1) ** 2 - 1, 3))
     if log_scales is None:  # the seeded-points branch (gstex.py:285-301)
         if n <= 3:
             raise ValueError(f"{n} points: the scale of a point is the mean distance to its 3 nearest neighbours")
-        d = torch.from_numpy(knn_mean_dist(means.numpy(), 3))
+        d = torch.from_numpy(knn_mean_dist(means.numpy(), 3, device=knn_device))
         log_scales = torch.log(d[:, None].repeat(1, 3))
         quats = random_quat_tensor(n, generator=torch.Generator().manual_seed(int(seed)))
         opacity = torch.logit(0.1 * torch.ones(n, 1))
     return _one_texel_scene(means, log_scales, quats, opacity, features_dc, features_rest)
 
 
-def scene_from_point_cloud(path, fix_lod_init: bool = False, sh_degree: int = 3, seed: int = 42) -> Scene:
+def scene_from_point_cloud(path, fix_lod_init: bool = False, sh_degree: int = 3, seed: int = 42,
+                           knn_device=None) -> Scene:
     """`init_lod_ply` (load_from_lod_ply, gstex.py:672-694; the seeded-points branch, gstex.py:278-301, 314-328): a
     point cloud with x y z and red green blue in 0..255.  features_dc = RGB2SH(colour / 255), features_rest zero,
     log-scales the log of the mean distance to the 3 nearest neighbours (x3), uniform random unit quaternions from a
-    CPU generator seeded with `seed` (the reference draws them from the global generator), opacity logit(0.1)."""
+    CPU generator seeded with `seed` (the reference draws them from the global generator), opacity logit(0.1).
+    knn_device: where the neighbour distances are computed; None (the default) is cKDTree on the host, a HIP device
+    the grid kernels of gstex_amd.neighbors (scene.knn_mean_dist)."""
     deg = _check_degree(sh_degree)
     cols = read_ply(path)
     means = _columns(cols, ("x", "y", "z"), path)
     colors = _columns(cols, ("red", "green", "blue"), path)
     if fix_lod_init:
         means = axis_fix_points(means)
-    return _seeded_scene(means, RGB2SH(colors / 255), deg, seed=seed)
+    return _seeded_scene(means, RGB2SH(colors / 255), deg, seed=seed, knn_device=knn_device)
 
 
 INIT_NPZ_KEYS = ("xyz", "colors", "opacity", "scaling", "rotation")

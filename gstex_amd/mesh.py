@@ -472,3 +472,65 @@ def mesh_grid(lo, hi, voxel_size=None, mesh_res: int = 256, sdf_trunc=None):
     lo_p, hi_p = lo - pad, hi + pad
     dims = tuple(max(2, int(np.ceil((hi_p[c] - lo_p[c]) / h - 1e-9)) + 1) for c in range(3))
     return tuple(float(v) for v in lo_p), h, dims, trunc, (lo_p, hi_p)
+
+
+# ---------------------------------------------------------------------------------------- scoring
+def sample_mesh(vertices, faces, spacing):
+    """gstex_amd.neighbors.sample_mesh: the deterministic area sampler, -> (samples, weights, face_of)."""
+    from .neighbors import sample_mesh as _sample
+
+    return _sample(vertices, faces, spacing)
+
+
+def _crop(points, bounds):
+    lo = torch.as_tensor(bounds[0], dtype=torch.float32, device=points.device)
+    hi = torch.as_tensor(bounds[1], dtype=torch.float32, device=points.device)
+    return ((points >= lo[None]) & (points <= hi[None])).all(dim=1)
+
+
+def score_mesh(vertices, faces, reference, *, spacing, max_dist=None, thresholds=(), bounds=None) -> dict:
+    """A mesh against a reference point cloud, by the DTU protocol's measures, on the mesh's device (HIP: the kernels
+    of gstex_amd.neighbors; CPU: their twins).  The surface is sampled at `spacing` (sample_mesh); d_i is the distance
+    from sample i (area weight w_i) to its nearest reference point and e_j that from reference point j to its nearest
+    sample, both clamped at max_dist when given:
+
+        accuracy      sum w_i d_i / sum w_i          completeness   mean_j e_j         chamfer   their mean
+        precision[t]  sum w_i [d_i <= t] / sum w_i   recall[t]      mean_j [e_j <= t]  fscore[t] 2 P R / (P + R), 0 at 0/0
+
+    precision, recall and fscore are lists aligned with `thresholds`.  bounds = (lo, hi) crops samples and reference
+    points to the box first (the protocol's observation box).  The dict also holds d (S,), e (R,) (f32, on the
+    device), samples, weights, n_samples and n_reference.  The kernels return squared distances; the (correctly rounded) roots,
+    the clamps and the float64 sums are torch ops."""
+    from .neighbors import PointGrid, sqrt_rn
+
+    vertices = vertices.detach().to(torch.float32)
+    reference = reference.detach().to(device=vertices.device, dtype=torch.float32)
+    if reference.dim() != 2 or reference.shape[1] != 3:
+        raise ValueError("reference: expected an (R, 3) tensor")
+    samples, weights, _ = sample_mesh(vertices, faces, spacing)
+    if bounds is not None:
+        keep = _crop(samples, bounds)
+        samples, weights = samples[keep].contiguous(), weights[keep].contiguous()
+        reference = reference[_crop(reference, bounds)]
+    reference = reference.contiguous()
+    if samples.shape[0] == 0 or reference.shape[0] == 0:
+        raise ValueError(f"score_mesh: nothing to compare ({samples.shape[0]} samples, {reference.shape[0]} reference "
+                         "points)")
+    d = sqrt_rn(PointGrid(reference).query(samples, k=1)[0][:, 0])
+    e = sqrt_rn(PointGrid(samples).query(reference, k=1)[0][:, 0])
+    if max_dist is not None:
+        d, e = d.clamp(max=float(max_dist)), e.clamp(max=float(max_dist))
+    w = weights.double()
+    w_sum = w.sum()
+    accuracy = float((w * d.double()).sum() / w_sum)
+    completeness = float(e.double().mean())
+    out = dict(accuracy=accuracy, completeness=completeness, chamfer=0.5 * (accuracy + completeness),
+               thresholds=tuple(float(t) for t in thresholds), precision=[], recall=[], fscore=[], d=d, e=e,
+               samples=samples, weights=weights, n_samples=int(samples.shape[0]), n_reference=int(reference.shape[0]))
+    for t in out["thresholds"]:
+        p = float((w * (d <= t).double()).sum() / w_sum)
+        r = float((e <= t).double().mean())
+        out["precision"].append(p)
+        out["recall"].append(r)
+        out["fscore"].append(2 * p * r / (p + r) if p + r > 0 else 0.0)
+    return out

@@ -565,6 +565,24 @@ class GStexTrainer:
             faces = torch.from_numpy(f).to(self.device)
         return vertices, colors, faces
 
+    @torch.no_grad()
+    def score_mesh(self, views, reference, *, spacing: float, max_dist: float | None = None, thresholds=(),
+                   score_bounds=None, **extract_kw) -> dict:
+        """extract_mesh(views, **extract_kw) scored against a reference point cloud (R, 3) by gstex_amd.mesh.score_mesh
+        (accuracy, completeness, chamfer and per threshold precision, recall, fscore), all on the device.  spacing: the
+        surface sampler's; score_bounds: score_mesh's `bounds`, the observation box (extract_mesh's own `bounds` goes in
+        extract_kw).  The dict also holds the mesh as vertices, colors and faces.  Like extract_mesh it leaves the
+        training state alone."""
+        from .mesh import score_mesh
+
+        extract_kw.setdefault("color", False)
+        vertices, colors, faces = self.extract_mesh(views, **extract_kw)
+        ref = torch.as_tensor(reference, dtype=torch.float32).to(self.device)
+        out = score_mesh(vertices, faces, ref, spacing=spacing, max_dist=max_dist, thresholds=thresholds,
+                         bounds=score_bounds)
+        out.update(vertices=vertices, colors=colors, faces=faces)
+        return out
+
     def _mesh_render(self, view: View, color: bool) -> dict:
         """One view's inputs of TSDFVolume.integrate: the un-normalised depth, alpha and the composited colour."""
         r = self.render(view, composite=False, geometry=True)

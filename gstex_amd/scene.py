@@ -20,7 +20,14 @@ BLENDER_FOV = 0.6911112
 CAM_RADIUS = 4.0311
 
 
-def knn_mean_dist(points: np.ndarray, k: int = 3) -> np.ndarray:
+def knn_mean_dist(points: np.ndarray, k: int = 3, device=None) -> np.ndarray:
+    """The mean distance of each point to its k nearest other points.  device None (the default): cKDTree on the host.
+    A device: gstex_amd.neighbors.knn_mean_dist_device there (a HIP device: the grid kernels; "cpu": their twins)."""
+    if device is not None:
+        from .neighbors import knn_mean_dist_device
+
+        pts = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32)).to(device)
+        return knn_mean_dist_device(pts, k).cpu().numpy()
     from scipy.spatial import cKDTree
 
     tree = cKDTree(points)

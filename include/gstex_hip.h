@@ -848,6 +848,83 @@ typedef struct gstex_mesh_extract_args {
 int gstex_mesh_extract_mark(const gstex_mesh_extract_args* args, void* stream);
 int gstex_mesh_extract_emit(const gstex_mesh_extract_args* args, void* stream);
 
+/* ---- mesh scoring: grid nearest neighbours and a mesh surface sampler -- added within ABI 19 (additive); not in the
+ * reference (DESIGN.md "Mesh scoring and nearest neighbours") ----------------------------------------------------------
+ * A uniform grid over a 3D point set.  origin is the component-wise minimum of the points, and the cell of p is, per
+ * axis, (int)((p - origin) / cell_size) (one rounded subtraction, one rounded division) clamped to [0, n_axis - 1];
+ * the linear cell index is (cz * ny + cy) * nx + cx.  For an exact query the dims must cover the points (no point
+ * clamped): n_axis = (int)((max - origin) / cell_size) + 1 by the same two operations.  Every dim must be in
+ * [1, GSTEX_NN_MAX_AXIS_CELLS] and nx * ny * nz at most GSTEX_NN_MAX_CELLS (UNSUPPORTED beyond either), point counts
+ * below 2^31.  Every value is computed by individually rounded fp32 operations in the order DESIGN.md states. */
+#define GSTEX_NN_MAX_CELLS (1 << 26)
+#define GSTEX_NN_MAX_AXIS_CELLS 4096
+#define GSTEX_NN_MAX_K 8
+typedef struct gstex_nn_grid {
+    float origin[3];
+    float cell_size;
+    int32_t nx, ny, nz;
+} gstex_nn_grid;
+/* Build: gstex_nn_grid_count zeroes cell_count[n_cells] and adds one per point (integer atomics); the caller scans it
+ * with gstex_scan_offsets into cell_start[n_cells + 1]; gstex_nn_grid_place zeroes cursor[n_cells] and writes each
+ * point into its cell's segment as one 16-byte record (x, y, z, the point's index as int32 bits): records (n, 4),
+ * 16-byte aligned.  The order inside a cell is unspecified.  points: DEVICE (n, 3) fp32. */
+int gstex_nn_grid_count(const gstex_nn_grid* grid, int64_t n, const float* points, int32_t* cell_count, void* stream);
+int gstex_nn_grid_place(const gstex_nn_grid* grid, int64_t n, const float* points, const int32_t* cell_start,
+                        int32_t* cursor, float* records, void* stream);
+/* gstex_nn_query: for each query the k (1..GSTEX_NN_MAX_K) nearest points, exactly as brute force over all points
+ * gives them: d2 = (dx*dx + dy*dy) + dz*dz with dx = q.x - p.x, ascending, ties to the lower point index; missing
+ * neighbours are d2 = +inf, index = -1.  queries are records too, (n_queries, 4): (x, y, z, row); the results of a
+ * query go to row `row` of d2 (n_queries, k) and index (n_queries, k), and the queries are best issued in the order of
+ * their own grid cells (gstex_nn_grid_count / _place on them).  exclude_self != 0 skips the point whose index equals
+ * the query's row.  max_radius (>= 0, +inf for none): points with d2 > max_radius * max_radius do not count.  One
+ * thread per query walks Chebyshev rings of cells around the query's unclamped cell, intersected with the grid, until
+ * ((float)r * cell_size) * (1 - 2^-10), squared, reaches min(k-th best d2, max_radius^2) (r >= 1) or the ring has
+ * left the grid on every side.  No read-back. */
+typedef struct gstex_nn_query_args {
+    gstex_nn_grid grid;
+    int64_t n_points;
+    const int32_t* cell_start; /* (n_cells + 1) */
+    const float* records;      /* (n_points, 4) */
+    int64_t n_queries;
+    const float* queries;      /* (n_queries, 4) */
+    int32_t k;
+    int32_t exclude_self;
+    float max_radius;
+    float* d2;      /* (n_queries, k) */
+    int32_t* index; /* (n_queries, k) */
+} gstex_nn_query_args;
+int gstex_nn_query(const gstex_nn_query_args* args, void* stream);
+
+/* A deterministic area sampler of a triangle mesh.  Face (a, b, c) with longest edge L gets n = max(1, ceil(L /
+ * spacing)) and is split into n^2 congruent sub-triangles with one sample at each centroid: upright (i, j),
+ * i + j <= n - 1, at barycentric u = (i + 1/3) / n of b and v = (j + 1/3) / n of c; inverted (i, j), i + j <= n - 2, at
+ * ((i + 2/3) / n, (j + 2/3) / n); position (a + u * (b - a)) + v * (c - a) per component, weight area / n^2.  Order:
+ * ascending face, then i, then j, upright before inverted.
+ *   gstex_mesh_sample_mark  count[f] = n^2 (0 for a face with n > GSTEX_SAMPLE_MAX_N or an index outside the
+ *                           vertices) and stats (zeroed here first): int32[4] = the 64-bit sum of n^2 over the valid
+ *                           faces (low word, high word), the largest n (capped at 2^30), the number of faces with an
+ *                           index outside [0, n_vertices);
+ *   gstex_scan_offsets over count (the caller), ONE read-back of stats;
+ *   gstex_mesh_sample_emit  samples (n_samples, 3), weights (n_samples), face_of (n_samples); nothing is written past
+ *                           n_samples rows. */
+#define GSTEX_SAMPLE_MAX_N 256
+typedef struct gstex_mesh_sample_args {
+    int64_t n_vertices;
+    int64_t n_faces;
+    const float* vertices; /* (n_vertices, 3) */
+    const int32_t* faces;  /* (n_faces, 3) */
+    float spacing;
+    int32_t* count;         /* (n_faces); mark */
+    int32_t* stats;         /* int32[4], 8-byte aligned; mark */
+    const int32_t* offsets; /* (n_faces + 1); emit only */
+    int64_t n_samples;      /* emit only: rows of the outputs */
+    float* samples;
+    float* weights;
+    int32_t* face_of;
+} gstex_mesh_sample_args;
+int gstex_mesh_sample_mark(const gstex_mesh_sample_args* args, void* stream);
+int gstex_mesh_sample_emit(const gstex_mesh_sample_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
