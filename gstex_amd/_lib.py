@@ -216,6 +216,13 @@ class GstexMeshSampleArgs(ctypes.Structure):
                 ("n_samples", c_int64), ("samples", c_void_p), ("weights", c_void_p), ("face_of", c_void_p)]
 
 
+class GstexClusterArgs(ctypes.Structure):
+    """gstex_cluster_args (added within ABI 19): the walks of the splat clustering (degree, link, assign)."""
+    _fields_ = [("grid", GstexNnGrid), ("n", c_int64), ("cell_start", c_void_p), ("records", c_void_p),
+                ("shapes", c_void_p), ("eps", c_float), ("min_pts", c_int32), ("degree", c_void_p),
+                ("parent", c_void_p), ("offsets", c_void_p), ("labels", c_void_p)]
+
+
 TSDF_MAX_VIEWS = 8  # GSTEX_TSDF_MAX_VIEWS
 NN_MAX_CELLS = 1 << 26  # GSTEX_NN_MAX_CELLS
 NN_MAX_AXIS_CELLS = 4096  # GSTEX_NN_MAX_AXIS_CELLS
@@ -314,6 +321,12 @@ SIGNATURES = {
     "gstex_nn_query": (c_int32, [POINTER(GstexNnQueryArgs), _P]),
     "gstex_mesh_sample_mark": (c_int32, [POINTER(GstexMeshSampleArgs), _P]),
     "gstex_mesh_sample_emit": (c_int32, [POINTER(GstexMeshSampleArgs), _P]),
+    "gstex_cluster_shapes": (c_int32, [c_int64, _P, _P, c_int32, _P, _P, _P]),
+    "gstex_cluster_degree": (c_int32, [POINTER(GstexClusterArgs), _P]),
+    "gstex_cluster_link": (c_int32, [POINTER(GstexClusterArgs), _P]),
+    "gstex_cluster_roots": (c_int32, [c_int64, c_int32, _P, _P, _P, _P]),
+    "gstex_cluster_assign": (c_int32, [POINTER(GstexClusterArgs), _P]),
+    "gstex_cluster_pair_w2": (c_int32, [c_int64, _P, _P, c_int32, _P, c_int64, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

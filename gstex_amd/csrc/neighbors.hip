@@ -11,8 +11,7 @@
 // Between count and place, and between mark and emit, the caller runs gstex_scan_offsets.  Every value is one
 // individually rounded fp32 operation in a fixed order (-ffp-contract=off; sqrtf and / are the correctly rounded ones),
 // so gstex_amd.neighbors' eager twins reproduce every ordered output bit for bit.
-#include "gstex_common.h"
-#include "gstex_error.h"
+#include "nn_grid.h"
 
 using namespace gstex;
 
@@ -20,13 +19,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxK = GSTEX_NN_MAX_K;
-constexpr float kCellLimit = 536870912.0f;    // 2^29: a query's unclamped cell is kept within +-2^29 per axis
-constexpr float kRingMargin = 0.9990234375f;  // 1 - 2^-10 (the rounding of the cell assignment)
-
-struct GridK {
-    float ox, oy, oz, h;
-    int nx, ny, nz;
-};
 
 // (int)((p - o) / h) clamped to [0, n - 1]; p >= o for the points the grid was sized for
 __device__ __forceinline__ int point_cell_axis(float p, float o, float h, int n) {
@@ -61,13 +53,6 @@ __global__ __launch_bounds__(kThreads) void nn_place_kernel(const GridK g, int n
     const int slot = cell_start[c] + atomicAdd(&cursor[c], 1);
     if (slot < 0 || slot >= n) return;  // offsets that are not this point set's scan must not make the write leave
     records[slot] = make_float4(x, y, z, __int_as_float(i));
-}
-
-// the query's unclamped cell along one axis: floor((q - o) / h), kept within +-2^29 (a query that far outside is
-// farther from the grid than its kept cell says, so the ring bound stays a lower bound)
-__device__ __forceinline__ int query_cell_axis(float q, float o, float h) {
-    const float t = floorf((q - o) / h);
-    return (int)fminf(fmaxf(t, -kCellLimit), kCellLimit);  // (NaN -> -2^29)
 }
 
 struct QueryK {
@@ -281,31 +266,6 @@ __global__ __launch_bounds__(kThreads) void sample_emit_kernel(const SampleK a) 
     a.weights[s] = area / (fn * fn);
     a.face_of[s] = f;
 }
-
-inline bool finite_f(float x) { return x == x && x - x == 0.0f; }
-inline bool aligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) == 0; }
-
-int check_grid(const char* who, const gstex_nn_grid* grid, GridK& g) {
-    GSTEX_REQUIRE(grid, "%s: null grid", who);
-    GSTEX_REQUIRE(finite_f(grid->cell_size) && grid->cell_size > 0.0f, "%s: cell_size must be finite and > 0 (got %g)",
-                  who, (double)grid->cell_size);
-    GSTEX_REQUIRE(finite_f(grid->origin[0]) && finite_f(grid->origin[1]) && finite_f(grid->origin[2]),
-                  "%s: the origin must be finite", who);
-    GSTEX_REQUIRE(grid->nx >= 1 && grid->ny >= 1 && grid->nz >= 1, "%s: every dim must be >= 1 (got nx=%d, ny=%d, "
-                  "nz=%d)", who, grid->nx, grid->ny, grid->nz);
-    const long long cells = (long long)grid->nx * grid->ny * grid->nz;
-    if (grid->nx > GSTEX_NN_MAX_AXIS_CELLS || grid->ny > GSTEX_NN_MAX_AXIS_CELLS ||
-        grid->nz > GSTEX_NN_MAX_AXIS_CELLS || cells > GSTEX_NN_MAX_CELLS) {
-        set_error("%s: too many cells (nx=%d, ny=%d, nz=%d; at most %d per axis and %d in all)", who, grid->nx,
-                  grid->ny, grid->nz, GSTEX_NN_MAX_AXIS_CELLS, GSTEX_NN_MAX_CELLS);
-        return GSTEX_ERR_UNSUPPORTED;
-    }
-    g.ox = grid->origin[0]; g.oy = grid->origin[1]; g.oz = grid->origin[2]; g.h = grid->cell_size;
-    g.nx = grid->nx; g.ny = grid->ny; g.nz = grid->nz;
-    return GSTEX_OK;
-}
-
-inline long long cells_of(const GridK& g) { return (long long)g.nx * g.ny * g.nz; }
 
 template <int K>
 void launch_query(const QueryK& a, hipStream_t st) {

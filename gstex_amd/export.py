@@ -127,6 +127,32 @@ def score_mesh_ply(trainer, views, reference_ply, **kw) -> dict:
     return trainer.score_mesh(views, torch.from_numpy(ref), **kw)
 
 
+def cluster_ply(ply_in, ply_out, eps, min_pts, sh_degree: int = 3, fix_init: bool = False, report=None,
+                device=None):
+    """The reference's demo_ballquery_dbscan.py as a function: read a 2DGS checkpoint PLY
+    (gstex_amd.init.scene_from_2dgs_ply), cluster its splats (gstex_amd.cluster.dbscan on the scene's activation; on
+    `device`, default the HIP device when there is one), and write a point PLY of the centres: float x y z, int
+    `label` (1..K, -1 noise) and uchar red green blue from cluster.label_colors' fixed hash.  report: a path for
+    cluster.cluster_report's text (opacities activated, the two in-plane scales).  -> the ClusterResult."""
+    from .cluster import cluster_report, dbscan, label_colors
+    from .init import scene_from_2dgs_ply
+    from .ply import write_ply
+
+    scene = scene_from_2dgs_ply(ply_in, sh_degree=sh_degree, fix_init=fix_init)
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    with torch.no_grad():
+        means, scales, quats, opacities = (t.to(device) for t in scene.activated())
+        res = dbscan(means, scales[:, :2], quats, eps, min_pts)
+        if report is not None:
+            cluster_report(report, res, means, opacities, scales[:, :2])
+    xyz = means.cpu().numpy().astype(np.float32)
+    rgb = label_colors(res.labels)
+    write_ply(ply_out, {"x": xyz[:, 0], "y": xyz[:, 1], "z": xyz[:, 2], "label": res.labels.cpu().numpy().astype(np.int32),
+                        "red": rgb[:, 0], "green": rgb[:, 1], "blue": rgb[:, 2]}, binary=True)
+    return res
+
+
 def trainer_from_npz(path, device, **trainer_kwargs):
     """A GStexTrainer holding exactly the exported parameters (fresh optimizer state)."""
     from .model import GStexTrainer

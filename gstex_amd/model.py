@@ -583,6 +583,26 @@ class GStexTrainer:
         out.update(vertices=vertices, colors=colors, faces=faces)
         return out
 
+    # ------------------------------------------------------------------ clustering
+    @torch.no_grad()
+    def activated_splats(self):
+        """The step's activation of the geometry (gstex.py:1059-1066) in torch: -> (means, in-plane scales (n, 2) =
+        clamp(exp(log-scales), 1e-9), unit quats), detached."""
+        quats = self.quats.detach() / self.quats.detach().norm(dim=-1, keepdim=True)
+        scales = torch.exp(self.scales.detach()[:, :2]).clamp(min=1e-9)
+        return self.means.detach(), scales, quats
+
+    @torch.no_grad()
+    def cluster(self, eps: float, min_pts: int, cell_size: float | None = None):
+        """DBSCAN of the trainer's splats under the squared 2-Wasserstein distance (gstex_amd.cluster.dbscan on
+        activated_splats(), DESIGN.md "Clustering the splats"): -> ClusterResult(labels, degree, core, n_clusters) on
+        the device.  eps bounds the SQUARED distance.  Like extract_mesh it leaves the training state alone (a
+        pending deferred texel update is run first)."""
+        from .cluster import dbscan
+
+        self.wait_texture()
+        return dbscan(*self.activated_splats(), eps, min_pts, cell_size=cell_size)
+
     def _mesh_render(self, view: View, color: bool) -> dict:
         """One view's inputs of TSDFVolume.integrate: the un-normalised depth, alpha and the composited colour."""
         r = self.render(view, composite=False, geometry=True)

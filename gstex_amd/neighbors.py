@@ -376,9 +376,10 @@ class PointGrid:
     """A uniform-grid nearest-neighbour index over points (n, 3) fp32, built on the points' device (HIP: the kernels;
     CPU: the twins).  origin (the component-wise minimum), cell_size, dims (nx, ny, nz), cell_start (n_cells + 1) int32
     and records (n, 4) f32 = (x, y, z, index bits), a cell's records contiguous.  cell_size: default
-    default_cell_size(n, bounds), enlarged to fit the cell limits; an explicit one that does not fit is refused."""
+    default_cell_size(n, bounds), enlarged to fit the cell limits; an explicit one that does not fit is refused, or,
+    with fit=True, enlarged by a quarter at a time until it does."""
 
-    def __init__(self, points, cell_size=None):
+    def __init__(self, points, cell_size=None, fit: bool = False):
         if not (isinstance(points, torch.Tensor) and points.dim() == 2 and points.shape[1] == 3):
             raise ValueError("points: expected an (n, 3) tensor")
         if points.shape[0] < 1 or points.shape[0] >= 1 << 31:
@@ -396,6 +397,10 @@ class PointGrid:
             self.cell_size = _f32(cell_size)
             if not (self.cell_size > 0 and math.isfinite(self.cell_size)):
                 raise ValueError(f"cell_size must be finite and > 0 (got {cell_size})")
+            if fit:  # (as the default: no cell below 2^-20 of the longest extent)
+                self.cell_size = max(self.cell_size, _f32(float((hi - lo).max()) * 2.0 ** -20))
+            while fit and not _fits(grid_dims(lo, hi, self.cell_size)):
+                self.cell_size = _f32(self.cell_size * 1.25)
         self.dims = grid_dims(lo, hi, self.cell_size)
         if self.device.type == "cuda":
             self.cell_start, self.records = grid_build(self.points, self.origin, self.cell_size, self.dims)

@@ -925,6 +925,58 @@ typedef struct gstex_mesh_sample_args {
 int gstex_mesh_sample_mark(const gstex_mesh_sample_args* args, void* stream);
 int gstex_mesh_sample_emit(const gstex_mesh_sample_args* args, void* stream);
 
+/* ---- clustering the splats: DBSCAN under the squared 2-Wasserstein distance -- added within ABI 19 (additive); the
+ * reference's dbscan_clustering/dbscan_ballquery.py (DESIGN.md "Clustering the splats") --------------------------------
+ * A splat is a flat Gaussian: mean mu, unit quaternion (w, x, y, z) with rotation R, activated in-plane scales s0, s1
+ * (the first two columns of scales (n, scale_cols >= 2); the third scale counts as zero).  Its shape is
+ *   a = s0 R[:, 0] = s0 (1 - 2 (y y + z z), 2 (x y + w z), 2 (x z - w y)),
+ *   b = s1 R[:, 1] = s1 (2 (x y - w z), 1 - 2 (x x + z z), 2 (y z + w x)),      T = s0 s0 + s1 s1,
+ * and the distance of splats i and j is, every operation individually rounded in fp32 in this order,
+ *   d2   = (dx dx + dy dy) + dz dz,  dx = mu_i.x - mu_j.x                                   (as gstex_nn_query)
+ *   m00 = (a_i.x a_j.x + a_i.y a_j.y) + a_i.z a_j.z,  m01 = a_i . b_j,  m10 = b_i . a_j,  m11 = b_i . b_j  (same order)
+ *   fro  = (m00 m00 + m11 m11) + (m01 m01 + m10 m10),   det = m00 m11 - m01 m10
+ *   tr   = max((T_i + T_j) - 2 sqrtf(fro + 2 |det|), 0),   w2 = d2 + tr
+ * which is the same for (i, j) and (j, i) bit for bit; w2 >= d2 holds in fp32, so the grid prunes on d2 <= eps.  j is a
+ * neighbour of i iff j != i and w2 <= eps: eps is a threshold on the SQUARED distance, as in the reference.
+ *   degree[i] = the number of neighbours; core: degree[i] >= min_pts (self not counted); clusters: the connected
+ *   components of the cores; a cluster's id: 1 + the rank of its lowest core index among all clusters' lowest core
+ *   indices (1..K); a splat that is no core takes the lowest id among its core neighbours, or -1 (noise).
+ * Calls, on the grid of gstex_nn_grid_count / _place over the means (any cell size: the walk is gstex_nn_query's, with
+ * eps in the place of max_radius^2):
+ *   gstex_cluster_shapes   shapes (n, 8) = (a.xyz, T, b.xyz, 0) in the order of the grid's records, 16-byte aligned
+ *   gstex_cluster_degree   degree[index] and parent[index] = index
+ *   gstex_cluster_link     a core unites with every core neighbour of lower index: a lock-free union-find in parent
+ *                          (find with path halving, the higher root hooked under the lower by compare-and-swap; parents
+ *                          only ever decrease, so no walk can cycle and none waits for another lane)
+ *   gstex_cluster_roots    parent[i] = its root; root_flag[i] = 1 for a core that is its own root, else 0
+ *   gstex_scan_offsets over root_flag (the caller) -> offsets (n + 1); K = offsets[n], the ONE read-back
+ *   gstex_cluster_assign   labels[i] in the caller's order
+ * n == 0 is a no-op success; n >= 2^31, min_pts < 1, eps < 0 or not finite, null or misaligned pointers: INVALID_ARG. */
+typedef struct gstex_cluster_args {
+    gstex_nn_grid grid;
+    int64_t n;
+    const int32_t* cell_start; /* (n_cells + 1) */
+    const float* records;      /* (n, 4) */
+    const float* shapes;       /* (n, 8) */
+    float eps;
+    int32_t min_pts;
+    int32_t* degree;        /* (n) */
+    int32_t* parent;        /* (n) */
+    const int32_t* offsets; /* (n + 1); assign only */
+    int32_t* labels;        /* (n); assign only */
+} gstex_cluster_args;
+int gstex_cluster_shapes(int64_t n, const float* records, const float* scales, int32_t scale_cols, const float* quats,
+                         float* shapes, void* stream);
+int gstex_cluster_degree(const gstex_cluster_args* args, void* stream);
+int gstex_cluster_link(const gstex_cluster_args* args, void* stream);
+int gstex_cluster_roots(int64_t n, int32_t min_pts, const int32_t* degree, int32_t* parent, int32_t* root_flag,
+                        void* stream);
+int gstex_cluster_assign(const gstex_cluster_args* args, void* stream);
+/* d2, tr and w2 (n_pairs each) of the pairs (n_pairs, 2) int32 of splat indices, n_pairs < 2^30, from the caller's own
+ * arrays (means (n, 3), scales, quats (n, 4)); a pair with an index outside [0, n) gets NaN. */
+int gstex_cluster_pair_w2(int64_t n, const float* means, const float* scales, int32_t scale_cols, const float* quats,
+                          int64_t n_pairs, const int32_t* pairs, float* d2, float* tr, float* w2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
