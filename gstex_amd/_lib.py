@@ -223,6 +223,33 @@ class GstexClusterArgs(ctypes.Structure):
                 ("parent", c_void_p), ("offsets", c_void_p), ("labels", c_void_p)]
 
 
+SELECT_MAX_TENSORS = 4  # GSTEX_SELECT_MAX_TENSORS
+
+
+class GstexSelectPlanArgs(ctypes.Structure):
+    """gstex_select_plan_args (added within ABI 19): the rows and texels a per-splat mask keeps."""
+    _fields_ = [("n", c_int32), ("n_texels", c_int64)] + [
+        (name, c_void_p) for name in ("keep", "texture_dims", "rows", "texels", "flag")]
+
+
+class GstexSelectDimsArgs(ctypes.Structure):
+    """gstex_select_dims_args (added within ABI 19)."""
+    _fields_ = [("n", c_int32), ("n_new", c_int32)] + [
+        (name, c_void_p) for name in ("keep", "texture_dims", "row_off", "tex_off", "new_dims", "src_off")]
+
+
+class GstexSelectPair(ctypes.Structure):
+    """gstex_select_pair (added within ABI 19): one (src, dst) texel tensor of gstex_select_texels."""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p)]
+
+
+class GstexSelectTexelsArgs(ctypes.Structure):
+    """gstex_select_texels_args (added within ABI 19): the jagged gather."""
+    _fields_ = [("n_new", c_int32), ("channels", c_int32), ("n_tensors", c_int32), ("n_texels_new", c_int64),
+                ("n_texels", c_int64), ("new_dims", c_void_p), ("src_off", c_void_p),
+                ("tensors", GstexSelectPair * SELECT_MAX_TENSORS)]
+
+
 TSDF_MAX_VIEWS = 8  # GSTEX_TSDF_MAX_VIEWS
 NN_MAX_CELLS = 1 << 26  # GSTEX_NN_MAX_CELLS
 NN_MAX_AXIS_CELLS = 4096  # GSTEX_NN_MAX_AXIS_CELLS
@@ -327,6 +354,9 @@ SIGNATURES = {
     "gstex_cluster_roots": (c_int32, [c_int64, c_int32, _P, _P, _P, _P]),
     "gstex_cluster_assign": (c_int32, [POINTER(GstexClusterArgs), _P]),
     "gstex_cluster_pair_w2": (c_int32, [c_int64, _P, _P, c_int32, _P, c_int64, _P, _P, _P, _P, _P]),
+    "gstex_select_plan": (c_int32, [POINTER(GstexSelectPlanArgs), _P]),
+    "gstex_select_dims": (c_int32, [POINTER(GstexSelectDimsArgs), _P]),
+    "gstex_select_texels": (c_int32, [POINTER(GstexSelectTexelsArgs), _P]),
 }
 
 _lib = None

@@ -8,6 +8,7 @@ reference's dbscan_clustering/dbscan_ballquery.py; DESIGN.md "Clustering the spl
 * dbscan_eager           the brute-force twin: chunked O(N^2), no grid, labels by propagating the lowest core index
 * dbscan_walk_eager      the kernels restated on the host, walk for walk and hook for hook (tests, small sets)
 * pair_w2                gstex_cluster_pair_w2: (w2, d2, tr) of index pairs by the kernel
+* keep_mask              labels -> the bool mask GStexTrainer.select takes (chosen ids, or clusters of a minimum size)
 * cluster_summary / cluster_report / label_colors        the reference's analyze_clusters dictionary, its per-cluster
                          text report (statistics by index_add_ / scatter_reduce on the labels' device) and a colour per
                          label from a fixed hash
@@ -353,6 +354,31 @@ def dbscan(means, scales, quats, eps, min_pts, cell_size=None) -> ClusterResult:
     if not means.is_cuda:
         return dbscan_eager(means, scales, quats, eps, min_pts)
     return dbscan_device(means, scales, quats, eps, min_pts, cell_size)
+
+
+# ---------------------------------------------------------------------------------------- acting on the labels
+def keep_mask(labels_or_result, *, labels=None, min_size: int = 1, drop_noise: bool = True) -> torch.Tensor:
+    """The bool (n,) mask GStexTrainer.select takes, from a ClusterResult or its labels (n,), on the labels' device.
+    labels: the cluster ids to keep (min_size is then not applied); otherwise every cluster of at least min_size
+    members.  Noise (-1) is kept only with drop_noise=False."""
+    lab = labels_or_result.labels if isinstance(labels_or_result, ClusterResult) else torch.as_tensor(labels_or_result)
+    if lab.dim() != 1 or lab.dtype.is_floating_point or lab.dtype == torch.bool:
+        raise ValueError("keep_mask: expected integer labels of shape (n,)")
+    lab = lab.long()
+    member = lab >= 1
+    if labels is not None:
+        ids = torch.as_tensor(list(labels) if not isinstance(labels, torch.Tensor) else labels, dtype=torch.int64,
+                              device=lab.device).reshape(-1)
+        if bool((ids < 1).any()):
+            raise ValueError("keep_mask: cluster ids are >= 1 (noise is kept with drop_noise=False)")
+        keep = member & torch.isin(lab, ids)
+    else:
+        if int(min_size) < 1:
+            raise ValueError(f"keep_mask: min_size must be >= 1 (got {min_size})")
+        sizes = torch.bincount(lab[member])  # sizes[k]: members of cluster k
+        keep = member.clone()
+        keep[member] = sizes[lab[member]] >= int(min_size)
+    return keep if drop_noise else keep | (lab == -1)
 
 
 # ---------------------------------------------------------------------------------------- reports

@@ -939,6 +939,101 @@ class GStexTrainer:
         self._paint_acc, self._paint_scratch, self.test_colors, self._last_vis = None, {}, None, None
         return plan
 
+    # ------------------------------------------------------------------ selection
+    @torch.no_grad()
+    def select(self, keep):
+        """Keep the splats with keep[i] (a bool (n,) tensor on the trainer's device or the CPU), whatever their charts'
+        sizes (gstex_amd.select; DESIGN.md "Selecting splats"): plan, two scans, one read-back, then every per-splat
+        parameter's rows gathered and the texel store's kept blocks compacted into fresh tensors, with the Adam moments
+        the optimizer holds (kept rows and kept texels keep exp_avg and exp_avg_sq: no value changes, unlike
+        recharge(); every step count is kept).  Rebuilt for n_after splats and T_new texels: geometry_flat and its four
+        views, features_dc / features_rest, mappings (rows gathered, not recomputed: after a rechart they reflect the
+        scales at rechart time and the render must not change), texture_dims, n_texels, texture_dc (exactly T_new rows,
+        without spare capacity; one zero row when T_new == 0, since an empty store has no address to hand the raster),
+        the optimizer's groups and state and the texel gradient's buffers; the paint accumulator and scratch, the test
+        colours and the last visibility are dropped; the pair capacity, step_control and pixel_num stay.  ValueError on a
+        keep of the wrong shape or dtype or a malformed texture_dims row, RuntimeError under GradSync or when no splat
+        would remain, all with the trainer untouched; an all-true mask returns with the trainer untouched.  A
+        DensityController built for the old n must be rebuilt by the caller.  On a CPU trainer the eager twins run
+        instead of the kernels.  -> Selection(n_before, n_after, texels_before, texels_after)."""
+        from . import select as sel
+
+        n, d = self.means.shape[0], self.device
+        if self.texel_grad.routed:
+            raise RuntimeError("select: selection on a trainer under GradSync is not supported")
+        if not (isinstance(keep, torch.Tensor) and keep.dtype == torch.bool and tuple(keep.shape) == (n,)):
+            raise ValueError(f"select: keep must be a bool ({n},) tensor")
+        self.wait_texture()
+        dims, t_old = self.texture_dims, self.n_texels
+        plan = sel.plan_selection(dims, t_old, keep.to(dims.device))
+        if plan.flagged:
+            raise ValueError(f"select: {sel._MALFORMED} (n_texels = {t_old})")
+        if plan.n_new == 0:
+            raise RuntimeError("select: the mask would drop every splat")
+        if plan.n_new == n:
+            return sel.Selection(n, n, t_old, t_old)
+        opt, before = self.optimizer, self.param_groups()
+        attrs = {"xyz": "means", "features_dc": "features_dc", "features_rest": "features_rest",
+                 "opacity": "opacities", "scaling": "scales", "rotation": "quats", "texture_dc": "texture_dc"}
+
+        def moments(p):  # the two Adam moments the optimizer holds for p, or none
+            st = opt.state.get(p) or {}
+            return [st["exp_avg"], st["exp_avg_sq"]] if "exp_avg" in st else []
+
+        named = {"mappings": self.mappings}
+        for group, (p,) in before.items():
+            if group == "texture_dc":
+                continue
+            named[group] = p.detach()
+            for k, m in zip(("exp_avg", "exp_avg_sq"), moments(p)):
+                named[f"{group}.{k}"] = m
+        # the geometry parameters' shared allocation, segments 16-B aligned (as __init__)
+        m = plan.n_new
+        geo = [("xyz", 3), ("scaling", 3), ("rotation", 4), ("opacity", 1)]
+        flat = torch.zeros(sum((m * w + 3) // 4 * 4 for _, w in geo), device=d, dtype=torch.float32)
+        views, off = {}, 0
+        for group, w in geo:
+            views[group] = flat[off:off + m * w].view(m, w)
+            off += (m * w + 3) // 4 * 4
+
+        def alloc(name, shape):
+            v = views.get(name)
+            return v if v is not None else torch.empty(shape, device=d, dtype=torch.float32)
+
+        new = sel.select_rows(plan, named, alloc)
+        t_new = plan.n_texels_new
+        tex = self.texture_dc
+        srcs = [tex.detach()] + moments(tex)
+        if t_new == 0:  # only zero-texel charts are left: one zero row stands in for the empty store
+            new_dims, _ = sel.select_dims(dims, plan)
+            stores = [s.new_zeros((1,) + tuple(s.shape[1:])) for s in srcs]
+        else:
+            new_dims, stores = sel.apply_selection(dims, t_old, plan, srcs)
+        new["texture_dc"] = stores[0]
+        if len(stores) == 3:
+            new["texture_dc.exp_avg"], new["texture_dc.exp_avg_sq"] = stores[1], stores[2]
+        self.geometry_flat = flat
+        for group, attr in attrs.items():
+            setattr(self, attr, torch.nn.Parameter(new[group]))
+        after = self.param_groups()
+        for g in opt.param_groups:
+            old, p = before[g["name"]][0], after[g["name"]][0]
+            g["params"] = [p]
+            st = opt.state.pop(old, None)
+            if st:
+                st = dict(st)  # (the step count is kept)
+                if "exp_avg" in st:
+                    st["exp_avg"], st["exp_avg_sq"] = new[g["name"] + ".exp_avg"], new[g["name"] + ".exp_avg_sq"]
+                opt.state[p] = st
+        self.mappings = new["mappings"]
+        self.texture_dims = new_dims
+        self.n_texels = t_new
+        if self.defer_texture:  # fresh persistent gradient buffers for the new texel store
+            self.texel_grad.own(self.texture_dc, self.fused_step)
+        self.texel_grad.reset()
+        self._paint_acc, self._paint_scratch, self.test_colors, self._last_vis = None, {}, None, None
+        return sel.Selection(n, m, t_old, t_new)
+
     @torch.no_grad()
     def reset_opacity(self, value: float = 0.01):
         """The lineage's periodic opacity reset: every opacity logit capped at logit(value), the opacity parameter's

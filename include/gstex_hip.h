@@ -977,6 +977,68 @@ int gstex_cluster_assign(const gstex_cluster_args* args, void* stream);
 int gstex_cluster_pair_w2(int64_t n, const float* means, const float* scales, int32_t scale_cols, const float* quats,
                           int64_t n_pairs, const int32_t* pairs, float* d2, float* tr, float* w2, void* stream);
 
+/* ---- selecting splats: the jagged texel store compacted by a per-splat mask -- added within ABI 19 (additive); not in
+ * the reference, whose clustering tool writes a new file (DESIGN.md "Selecting splats") -------------------------------
+ * The texel store holds chart i's h_i * w_i texels of `channels` floats at rows [offset_i, offset_i + h_i * w_i), with
+ * texture_dims (n, 3) int32 = (h, w, offset); blocks may lie in any order and the store may have spare rows past
+ * n_texels.  Keeping the splats with keep[i] != 0, in their order:
+ *   gstex_select_plan    rows[i] = keep ? 1 : 0, texels[i] = keep ? h * w : 0; *flag |= 1 when ANY row, kept or not, is
+ *                        malformed: h < 0, w < 0, offset < 0, h * w > 2^31 - 1 or offset + h * w > n_texels (such a
+ *                        row counts 0 texels).  The caller zeroes *flag before the call.
+ *   gstex_scan_offsets over rows and over texels (the caller) -> row_off (n + 1), tex_off (n + 1); ONE read-back of
+ *                        (n_new, T_new, flag) = (row_off[n], tex_off[n], *flag)
+ *   gstex_select_dims    for a kept i, with j = row_off[i]: new_dims[j] = (h, w, tex_off[i]), src_off[j] = offset
+ *   gstex_select_texels  for every pair k, kept splat j (new index), t < h_j * w_j and c < channels:
+ *                          dst_k[(new_off_j + t) * channels + c] = src_k[(src_off_j + t) * channels + c]
+ *                        with new_off_j = new_dims[j][2].  Every destination word below n_texels_new * channels is
+ *                        written exactly once and none at or past it; no word at or past n_texels * channels is read.
+ *                        The chart of destination texel t is the LAST j with new_off_j <= t, which passes over
+ *                        zero-texel charts.  A texel that new_dims / src_off do not place inside the store (arrays that
+ *                        are not a plan's) is left unwritten.  src == dst is refused.
+ * Per-splat tensors go through gstex_density_apply with these rows, row_off as offsets and every kind KEEP.  No entry
+ * point allocates or synchronises; n == 0 (plan, dims) and n_texels_new == 0 or n_tensors == 0 (texels) are no-op
+ * successes.  Negative sizes, totals >= 2^31, channels outside [1, 8], n_tensors above the maximum, null or misaligned
+ * pointers: INVALID_ARG. */
+#define GSTEX_SELECT_MAX_TENSORS 4
+typedef struct gstex_select_plan_args {
+    int32_t n;
+    int64_t n_texels;
+    const uint8_t* keep;         /* (n) bytes, non-zero = keep */
+    const int32_t* texture_dims; /* (n, 3) */
+    int32_t* rows;               /* (n) */
+    int32_t* texels;             /* (n) */
+    int32_t* flag;               /* one word, zeroed by the caller */
+} gstex_select_plan_args;
+int gstex_select_plan(const gstex_select_plan_args* args, void* stream);
+
+typedef struct gstex_select_dims_args {
+    int32_t n;
+    int32_t n_new; /* row_off[n] as the host read it: rows of new_dims and src_off; nothing is written past them */
+    const uint8_t* keep;
+    const int32_t* texture_dims;
+    const int32_t* row_off; /* (n + 1) */
+    const int32_t* tex_off; /* (n + 1) */
+    int32_t* new_dims;      /* (n_new, 3) */
+    int32_t* src_off;       /* (n_new) */
+} gstex_select_dims_args;
+int gstex_select_dims(const gstex_select_dims_args* args, void* stream);
+
+typedef struct gstex_select_pair {
+    const float* src; /* (>= n_texels, channels) */
+    float* dst;       /* (>= n_texels_new, channels) */
+} gstex_select_pair;
+typedef struct gstex_select_texels_args {
+    int32_t n_new;
+    int32_t channels;
+    int32_t n_tensors;
+    int64_t n_texels_new; /* tex_off[n] as the host read it */
+    int64_t n_texels;     /* rows of every src that may be read */
+    const int32_t* new_dims;
+    const int32_t* src_off;
+    gstex_select_pair tensors[GSTEX_SELECT_MAX_TENSORS];
+} gstex_select_texels_args;
+int gstex_select_texels(const gstex_select_texels_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
