@@ -30,7 +30,7 @@ import torch
 
 from . import _lib
 from ._lib import ptr
-from .neighbors import PointGrid, _f32, _s, sqrt_rn
+from .neighbors import PointGrid, _f32, _s, grid_build_eager, sqrt_rn, walk_rings_eager
 
 
 @dataclass
@@ -182,30 +182,28 @@ def cluster_grid(means, eps, cell_size=None) -> PointGrid:
 # ---------------------------------------------------------------------------------------- the kernels on the host
 def dbscan_walk_eager(means, scales, quats, eps, min_pts, cell_size=None) -> ClusterResult:
     """gstex_cluster_degree / _link / _roots / _assign restated on the host in python loops (for tests and small sets):
-    the twin-built grid, each record's ring walk with the stop test, d2 <= eps before the trace term, the union-find
-    with path halving and the higher root hooked under the lower, the flags' exclusive scan and the second walk of the
-    splats that are no core.  Must equal dbscan_eager."""
+    the twin-built grid, each record's ring walk (neighbors.walk_rings_eager, stopped on eps), d2 <= eps before the
+    trace term, the union-find with path halving and the higher root hooked under the lower, the flags' exclusive scan
+    and the second walk of the splats that are no core.  Must equal dbscan_eager."""
     means, scales, quats = _splats(means.cpu(), scales.cpu(), quats.cpu())
     eps, min_pts = _check_params(eps, min_pts)
     n = means.shape[0]
     if n == 0:
         return _empty(means.device)
     f = np.float32
-    grid = cluster_grid(means, eps, cell_size)
-    rec = grid.records.numpy()
+    # the grid of the finite means (PointGrid refuses other bounds); the kernels place every record they are given,
+    # a NaN coordinate in cell 0, and walk from it by the query cell's own NaN rule
+    grid = cluster_grid(means[torch.isfinite(means).all(dim=1)], eps, cell_size)
+    cell_start, records = grid_build_eager(means, grid.origin, grid.cell_size, grid.dims)
+    rec = records.numpy()
     pts, idx = rec[:, :3], np.ascontiguousarray(rec[:, 3]).view(np.int32).astype(np.int64)
-    cs = grid.cell_start.numpy().astype(np.int64)
-    nx, ny, nz = grid.dims
-    h, o = f(grid.cell_size), [f(v) for v in grid.origin]
+    cs = cell_start.numpy().astype(np.int64)
     a, b, T = shapes_eager(scales, quats)
     a, b, T = a[idx], b[idx], T[idx]  # the shape records, in record order
-    e, margin = f(eps), f(1.0 - 2.0 ** -10)
+    e = f(eps)
 
     def neighbors_of(t):
         q = pts[t]
-        cx, cy, cz = (int(np.floor(f(f(q[c] - o[c]) / h))) for c in range(3))
-        r_first = max(-cx, cx - (nx - 1), -cy, cy - (ny - 1), -cz, cz - (nz - 1), 0)
-        r_last = max(cx, nx - 1 - cx, cy, ny - 1 - cy, cz, nz - 1 - cz)
         out = []
 
         def scan(p, pe):
@@ -219,22 +217,7 @@ def dbscan_walk_eager(means, scales, quats, eps, min_pts, cell_size=None) -> Clu
                 tr = _trace_eager(a[t], b[t], T[t], a[s], b[s], T[s]).numpy()
                 out.extend(int(v) for v in idx[p:pe][near[(d2[near] + tr) <= e]])
 
-        for r in range(r_first, r_last + 1):
-            x0, x1 = max(cx - r, 0), min(cx + r, nx - 1)
-            ends = [x for x in ((cx - r, cx + r) if r > 0 else (cx,)) if 0 <= x < nx]
-            for z in range(max(cz - r, 0), min(cz + r, nz - 1) + 1):
-                for y in range(max(cy - r, 0), min(cy + r, ny - 1) + 1):
-                    base = (z * ny + y) * nx
-                    if abs(z - cz) == r or abs(y - cy) == r:
-                        if x0 <= x1:
-                            scan(cs[base + x0], cs[base + x1 + 1])
-                    else:
-                        for x in ends:
-                            scan(cs[base + x], cs[base + x + 1])
-            if r >= 1:
-                lb = f(f(r) * h) * margin
-                if lb * lb >= e:
-                    break
+        walk_rings_eager(q, grid.origin, grid.cell_size, grid.dims, cs, scan, lambda: e)
         return out
 
     nbrs = {int(idx[t]): neighbors_of(t) for t in range(n)}

@@ -12,8 +12,8 @@
 // The grid is neighbors.hip's (gstex_nn_grid_count / _place on the means); between roots and assign the caller scans
 // the flags with gstex_scan_offsets.  Every value is one individually rounded fp32 operation in a fixed order
 // (-ffp-contract=off, correctly rounded sqrtf), so gstex_amd.cluster's eager twins reproduce d2, tr, w2 bit for bit and
-// the labels exactly.  The ring walk is a second statement of gstex_nn_query's, kept apart from it: that one carries
-// a sorted top-k through the rings and stops on its k-th best, this one visits every record within a fixed radius.
+// the labels exactly.  The ring walk is nn_grid.h's walk_rings, the one gstex_nn_query runs: that kernel carries a
+// sorted top-k through the rings and stops on its k-th best, these visit every record within the fixed radius eps.
 #include "nn_grid.h"
 
 using namespace gstex;
@@ -77,13 +77,11 @@ __device__ __forceinline__ float dist2(float qx, float qy, float qz, float px, f
 }
 
 // ---------------------------------------------------------------------------------------------- the walk
-// Every record within the fixed radius of record `slot`: on_neighbor(index) for each other splat with w2 <= eps.  The
-// rings, their rows and the stop test are gstex_nn_query's with eps in the place of max_radius^2: after ring r >= 1,
-// every record not yet visited is at least ((float)r h)(1 - 2^-10) away, and w2 >= d2.
+// Every record within the fixed radius of the record q: on_neighbor(index) for each other splat with w2 <= eps.
+// walk_rings stops on eps itself: what it has not visited is farther than that in d2, and w2 >= d2.
 template <class F>
 __device__ __forceinline__ void for_each_neighbor(const ClusterK& a, const float4& q, int self, const Shape& mine,
                                                   F&& on_neighbor) {
-    const GridK& g = a.g;
     auto scan = [&](int p, int pe) {
         p = max(p, 0); pe = min(pe, a.n);  // never outside the records
         for (; p < pe; ++p) {
@@ -95,44 +93,7 @@ __device__ __forceinline__ void for_each_neighbor(const ClusterK& a, const float
             if (w2 <= a.eps) on_neighbor(idx);
         }
     };
-    auto scan_row = [&](int base, bool face, int x0, int x1, int xl, int xr) {
-        if (face) {  // the row's cells x0..x1 are contiguous, and so are their records: one segment
-            if (x0 <= x1) scan(a.cell_start[base + x0], a.cell_start[base + x1 + 1]);
-            return;
-        }
-        if (xl >= 0 && xl < g.nx) scan(a.cell_start[base + xl], a.cell_start[base + xl + 1]);
-        if (xr >= 0 && xr < g.nx) scan(a.cell_start[base + xr], a.cell_start[base + xr + 1]);
-    };
-    const int cx = query_cell_axis(q.x, g.ox, g.h), cy = query_cell_axis(q.y, g.oy, g.h),
-              cz = query_cell_axis(q.z, g.oz, g.h);
-    const int out_x = max(max(-cx, cx - (g.nx - 1)), 0), out_y = max(max(-cy, cy - (g.ny - 1)), 0),
-              out_z = max(max(-cz, cz - (g.nz - 1)), 0);
-    const int r_first = max(max(out_x, out_y), out_z);
-    const int far_x = max(cx, (g.nx - 1) - cx), far_y = max(cy, (g.ny - 1) - cy), far_z = max(cz, (g.nz - 1) - cz);
-    const int r_last = max(max(far_x, far_y), far_z);
-    for (int r = r_first; r <= r_last; ++r) {
-        const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1);
-        const int y0 = max(cy - r, 0), y1 = min(cy + r, g.ny - 1);
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, g.nx - 1);
-        const int xl = cx - r, xr = r > 0 ? cx + r : -1;  // (ring 0: one cell, not twice)
-        const bool x_ends = (xl >= 0 && xl < g.nx) || (xr >= 0 && xr < g.nx);
-        for (int z = z0; z <= z1; ++z) {
-            const bool z_face = (z - cz == r) || (cz - z == r);
-            const int slab = z * g.ny;
-            if (z_face || x_ends) {
-                for (int y = y0; y <= y1; ++y)
-                    scan_row((slab + y) * g.nx, z_face || (y - cy == r) || (cy - y == r), x0, x1, xl, xr);
-            } else {  // only the rows on the ring's two y faces hold cells of it
-                const int ya = cy - r, yb = cy + r;
-                if (ya >= 0 && ya < g.ny) scan_row((slab + ya) * g.nx, true, x0, x1, xl, xr);
-                if (yb >= 0 && yb < g.ny) scan_row((slab + yb) * g.nx, true, x0, x1, xl, xr);
-            }
-        }
-        if (r >= 1) {
-            const float lb = ((float)r * g.h) * kRingMargin;
-            if (lb * lb >= a.eps) break;
-        }
-    }
+    walk_rings(a.g, a.cell_start, q.x, q.y, q.z, scan, [&] { return a.eps; });
 }
 
 // the record of thread t, refused unless its index is one of this set's

@@ -131,9 +131,6 @@ __global__ __launch_bounds__(kThreads) void density_apply_kernel(const ApplyArgs
     if (rows == 2) t.dst[(row0 + 1) * w + c] = out1;
 }
 
-inline bool finite_f(float x) { return x == x && x - x == 0.0f; }
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 }  // namespace
 
 extern "C" int gstex_density_accum(int32_t n, const float* means, const float* v_means, const gstex_camera* cam,
@@ -147,9 +144,9 @@ extern "C" int gstex_density_accum(int32_t n, const float* means, const float* v
     if (n == 0) return GSTEX_OK;
     GSTEX_REQUIRE(means && v_means && cam->viewmat && num_tiles_hit && extents && grad_sum && count && max_extent,
                   "gstex_density_accum: null pointer");
-    GSTEX_REQUIRE(aligned4(means) && aligned4(v_means) && aligned4(cam->viewmat) && aligned4(num_tiles_hit) &&
-                      aligned4(extents) && aligned4(skip) && aligned4(grad_sum) && aligned4(count) &&
-                      aligned4(max_extent),
+    GSTEX_REQUIRE(aligned(means, 4) && aligned(v_means, 4) && aligned(cam->viewmat, 4) && aligned(num_tiles_hit, 4) &&
+                      aligned(extents, 4) && aligned(skip, 4) && aligned(grad_sum, 4) && aligned(count, 4) &&
+                      aligned(max_extent, 4),
                   "gstex_density_accum: misaligned pointer (4-byte words)");
     const float hw = 0.5f * (float)cam->W, hh = 0.5f * (float)cam->H;
     density_accum_kernel<<<div_up(n, kThreads), kThreads, 0, as_stream(stream)>>>(
@@ -170,8 +167,8 @@ extern "C" int gstex_density_plan(const gstex_density_plan_args* args, void* str
     if (p.n == 0) return GSTEX_OK;
     GSTEX_REQUIRE(p.log_scales && p.opac_logits && p.grad_sum && p.count && p.max_extent && p.rows && p.kind,
                   "gstex_density_plan: null pointer");
-    GSTEX_REQUIRE(aligned4(p.log_scales) && aligned4(p.opac_logits) && aligned4(p.grad_sum) && aligned4(p.count) &&
-                      aligned4(p.max_extent) && aligned4(p.rows) && aligned4(p.kind),
+    GSTEX_REQUIRE(aligned(p.log_scales, 4) && aligned(p.opac_logits, 4) && aligned(p.grad_sum, 4) &&
+                      aligned(p.count, 4) && aligned(p.max_extent, 4) && aligned(p.rows, 4) && aligned(p.kind, 4),
                   "gstex_density_plan: misaligned pointer (4-byte words)");
     PlanArgs a;
     a.n = p.n; a.size_prune = p.size_prune ? 1 : 0; a.prune_only = p.prune_only ? 1 : 0;
@@ -194,8 +191,8 @@ extern "C" int gstex_density_apply(const gstex_density_apply_args* args, void* s
     GSTEX_REQUIRE(p.n_tensors == 0 || p.tensors, "gstex_density_apply: null tensor table");
     if (p.n == 0 || p.n_new == 0) return GSTEX_OK;
     GSTEX_REQUIRE(p.rows && p.kind && p.offsets, "gstex_density_apply: null pointer (rows / kind / offsets)");
-    GSTEX_REQUIRE(aligned4(p.rows) && aligned4(p.kind) && aligned4(p.offsets) && aligned4(p.scales) &&
-                      aligned4(p.quats_n) && aligned4(p.noise),
+    GSTEX_REQUIRE(aligned(p.rows, 4) && aligned(p.kind, 4) && aligned(p.offsets, 4) && aligned(p.scales, 4) &&
+                      aligned(p.quats_n, 4) && aligned(p.noise, 4),
                   "gstex_density_apply: misaligned pointer (4-byte words)");
     ApplyArgs a{};
     long long blocks = 0;
@@ -207,7 +204,7 @@ extern "C" int gstex_density_apply(const gstex_density_apply_args* args, void* s
                       "gstex_density_apply: tensor %d has an unknown role %d", i, t.role);
         if (t.width == 0) continue;
         GSTEX_REQUIRE(t.src && t.dst, "gstex_density_apply: tensor %d: null pointer", i);
-        GSTEX_REQUIRE(aligned4(t.src) && aligned4(t.dst), "gstex_density_apply: tensor %d: misaligned pointer", i);
+        GSTEX_REQUIRE(aligned(t.src, 4) && aligned(t.dst, 4), "gstex_density_apply: tensor %d: misaligned pointer", i);
         GSTEX_REQUIRE(t.src != t.dst, "gstex_density_apply: tensor %d: src and dst must differ", i);
         GSTEX_REQUIRE(t.role != GSTEX_DENSITY_ROLE_MEANS || (t.width == 3 && p.scales && p.quats_n && p.noise),
                       "gstex_density_apply: tensor %d: the means need width 3 and scales, quats_n and noise", i);

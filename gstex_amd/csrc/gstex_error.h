@@ -23,4 +23,8 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 inline int div_up(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// what the entry points ask of a float argument and of a pointer (bytes: a power of two)
+inline bool finite_f(float x) { return x == x && x - x == 0.0f; }
+inline bool aligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) == 0; }
+
 }  // namespace gstex

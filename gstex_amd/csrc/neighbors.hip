@@ -3,7 +3,7 @@
 //
 //   gstex_nn_grid_count     one thread per point: its cell's count, by integer atomics
 //   gstex_nn_grid_place     one thread per point: one 16-byte record (x, y, z, index) into its cell's segment
-//   gstex_nn_query          one thread per query: Chebyshev rings of cells around the query's cell, a sorted top-k in
+//   gstex_nn_query          one thread per query: nn_grid.h's ring walk around the query's cell, a sorted top-k in
 //                           registers (k compile-time), exact
 //   gstex_mesh_sample_mark  one thread per face: n^2 and the totals
 //   gstex_mesh_sample_emit  one thread per sample: its face by bisection of the offsets, then (i, j, upright / inverted)
@@ -93,17 +93,14 @@ __device__ __forceinline__ void scan_records(const QueryK& a, const float4& q, i
     }
 }
 
-// Row (z, y) of ring r.  On a face of the ring its cells x0..x1 are contiguous, and so are their records: one
-// segment.  Through the ring's inside: the two end cells cx - r and cx + r, where they are in the grid.
+// The ring walk of one query, the top-k carried through it.  A function of its own, the arrays its parameters, not a
+// call in the kernel with the kernel's arrays captured: the lambdas' closures are then gone before this is inlined
+// into the kernel, where the compiler turns bd and bi into vector registers only while nothing else holds their
+// address (as captures would); without that the k = 3 launch is 5 % slower (EXPERIMENTS.md "Nearest neighbours").
 template <int K>
-__device__ __forceinline__ void scan_row(const QueryK& a, const float4& q, int self, int base, bool face, int x0,
-                                         int x1, int xl, int xr, float (&bd)[K], int (&bi)[K]) {
-    if (face) {
-        if (x0 <= x1) scan_records<K>(a, q, self, a.cell_start[base + x0], a.cell_start[base + x1 + 1], bd, bi);
-        return;
-    }
-    if (xl >= 0 && xl < a.g.nx) scan_records<K>(a, q, self, a.cell_start[base + xl], a.cell_start[base + xl + 1], bd, bi);
-    if (xr >= 0 && xr < a.g.nx) scan_records<K>(a, q, self, a.cell_start[base + xr], a.cell_start[base + xr + 1], bd, bi);
+__device__ __forceinline__ void walk_query(const QueryK& a, const float4& q, int self, float (&bd)[K], int (&bi)[K]) {
+    walk_rings(a.g, a.cell_start, q.x, q.y, q.z, [&](int p, int pe) { scan_records<K>(a, q, self, p, pe, bd, bi); },
+               [&] { return fminf(bd[K - 1], a.r2max); });
 }
 
 template <int K>
@@ -114,47 +111,11 @@ __global__ __launch_bounds__(kThreads) void nn_query_kernel(const QueryK a) {
     const int row = __float_as_int(q.w);
     if (row < 0 || row >= a.n_queries) return;  // a record that is not one of this query set's rows
     const int self = a.exclude_self ? row : -1;
-    const GridK& g = a.g;
-    const int cx = query_cell_axis(q.x, g.ox, g.h), cy = query_cell_axis(q.y, g.oy, g.h),
-              cz = query_cell_axis(q.z, g.oz, g.h);
     float bd[K];
     int bi[K];
 #pragma unroll
     for (int s = 0; s < K; ++s) { bd[s] = INFINITY; bi[s] = -1; }
-
-    // the rings that meet the grid: from the Chebyshev distance of the cell to the grid's box ...
-    const int out_x = max(max(-cx, cx - (g.nx - 1)), 0), out_y = max(max(-cy, cy - (g.ny - 1)), 0),
-              out_z = max(max(-cz, cz - (g.nz - 1)), 0);
-    const int r_first = max(max(out_x, out_y), out_z);
-    // ... to the one that has left it on every side
-    const int far_x = max(cx, (g.nx - 1) - cx), far_y = max(cy, (g.ny - 1) - cy), far_z = max(cz, (g.nz - 1) - cz);
-    const int r_last = max(max(far_x, far_y), far_z);
-
-    for (int r = r_first; r <= r_last; ++r) {
-        const int z0 = max(cz - r, 0), z1 = min(cz + r, g.nz - 1);
-        const int y0 = max(cy - r, 0), y1 = min(cy + r, g.ny - 1);
-        const int x0 = max(cx - r, 0), x1 = min(cx + r, g.nx - 1);
-        const int xl = cx - r, xr = r > 0 ? cx + r : -1;  // (ring 0: one cell, not twice)
-        const bool x_ends = (xl >= 0 && xl < g.nx) || (xr >= 0 && xr < g.nx);
-        for (int z = z0; z <= z1; ++z) {
-            const bool z_face = (z - cz == r) || (cz - z == r);
-            const int slab = z * g.ny;
-            if (z_face || x_ends) {
-                for (int y = y0; y <= y1; ++y) {
-                    const bool face = z_face || (y - cy == r) || (cy - y == r);
-                    scan_row<K>(a, q, self, (slab + y) * g.nx, face, x0, x1, xl, xr, bd, bi);
-                }
-            } else {  // only the rows on the ring's two y faces hold cells of it
-                const int ya = cy - r, yb = cy + r;
-                if (ya >= 0 && ya < g.ny) scan_row<K>(a, q, self, (slab + ya) * g.nx, true, x0, x1, xl, xr, bd, bi);
-                if (yb >= 0 && yb < g.ny) scan_row<K>(a, q, self, (slab + yb) * g.nx, true, x0, x1, xl, xr, bd, bi);
-            }
-        }
-        if (r >= 1) {  // every point not yet visited lies in a ring beyond r
-            const float lb = ((float)r * g.h) * kRingMargin;
-            if (lb * lb >= fminf(bd[K - 1], a.r2max)) break;
-        }
-    }
+    walk_query<K>(a, q, self, bd, bi);
     const size_t o = (size_t)row * K;
 #pragma unroll
     for (int s = 0; s < K; ++s) {

@@ -131,8 +131,6 @@ __global__ __launch_bounds__(kThreads) void select_texels_kernel(const TexelArgs
     }
 }
 
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 }  // namespace
 
 extern "C" int gstex_select_plan(const gstex_select_plan_args* args, void* stream) {
@@ -142,11 +140,11 @@ extern "C" int gstex_select_plan(const gstex_select_plan_args* args, void* strea
     GSTEX_REQUIRE(p.n_texels >= 0 && p.n_texels < (1ll << 31),
                   "gstex_select_plan: n_texels must be in [0, 2^31) (got %lld)", (long long)p.n_texels);
     GSTEX_REQUIRE(p.flag, "gstex_select_plan: null pointer (flag)");
-    GSTEX_REQUIRE(aligned4(p.flag), "gstex_select_plan: misaligned pointer (flag; 4-byte words)");
+    GSTEX_REQUIRE(aligned(p.flag, 4), "gstex_select_plan: misaligned pointer (flag; 4-byte words)");
     if (p.n == 0) return GSTEX_OK;
     GSTEX_REQUIRE(p.keep && p.texture_dims && p.rows && p.texels,
                   "gstex_select_plan: null pointer (keep / texture_dims / rows / texels)");
-    GSTEX_REQUIRE(aligned4(p.texture_dims) && aligned4(p.rows) && aligned4(p.texels),
+    GSTEX_REQUIRE(aligned(p.texture_dims, 4) && aligned(p.rows, 4) && aligned(p.texels, 4),
                   "gstex_select_plan: misaligned pointer (texture_dims / rows / texels; 4-byte words)");
     select_plan_kernel<<<div_up(p.n, kThreads), kThreads, 0, as_stream(stream)>>>(
         p.n, (long long)p.n_texels, p.keep, p.texture_dims, p.rows, p.texels, p.flag);
@@ -162,8 +160,8 @@ extern "C" int gstex_select_dims(const gstex_select_dims_args* args, void* strea
     if (p.n == 0 || p.n_new == 0) return GSTEX_OK;
     GSTEX_REQUIRE(p.keep && p.texture_dims && p.row_off && p.tex_off && p.new_dims && p.src_off,
                   "gstex_select_dims: null pointer (keep / texture_dims / row_off / tex_off / new_dims / src_off)");
-    GSTEX_REQUIRE(aligned4(p.texture_dims) && aligned4(p.row_off) && aligned4(p.tex_off) && aligned4(p.new_dims) &&
-                      aligned4(p.src_off),
+    GSTEX_REQUIRE(aligned(p.texture_dims, 4) && aligned(p.row_off, 4) && aligned(p.tex_off, 4) &&
+                      aligned(p.new_dims, 4) && aligned(p.src_off, 4),
                   "gstex_select_dims: misaligned pointer (4-byte words)");
     GSTEX_REQUIRE(p.new_dims != p.texture_dims, "gstex_select_dims: new_dims and texture_dims must differ");
     select_dims_kernel<<<div_up(p.n, kThreads), kThreads, 0, as_stream(stream)>>>(
@@ -187,13 +185,13 @@ extern "C" int gstex_select_texels(const gstex_select_texels_args* args, void* s
                   "gstex_select_texels: n_texels_new > 0 needs n_new > 0 and n_texels > 0 (got %d, %lld)", p.n_new,
                   (long long)p.n_texels);
     GSTEX_REQUIRE(p.new_dims && p.src_off, "gstex_select_texels: null pointer (new_dims / src_off)");
-    GSTEX_REQUIRE(aligned4(p.new_dims) && aligned4(p.src_off),
+    GSTEX_REQUIRE(aligned(p.new_dims, 4) && aligned(p.src_off, 4),
                   "gstex_select_texels: misaligned pointer (new_dims / src_off; 4-byte words)");
     TexelArgs a{};
     for (int i = 0; i < p.n_tensors; ++i) {
         const gstex_select_pair& t = p.tensors[i];
         GSTEX_REQUIRE(t.src && t.dst, "gstex_select_texels: tensor %d: null pointer (src / dst)", i);
-        GSTEX_REQUIRE(aligned4(t.src) && aligned4(t.dst), "gstex_select_texels: tensor %d: misaligned pointer", i);
+        GSTEX_REQUIRE(aligned(t.src, 4) && aligned(t.dst, 4), "gstex_select_texels: tensor %d: misaligned pointer", i);
         GSTEX_REQUIRE(t.src != t.dst, "gstex_select_texels: tensor %d: src and dst must differ", i);
         a.t[i] = t;
     }

@@ -253,9 +253,6 @@ __global__ __launch_bounds__(kThreads) void mesh_emit_kernel(const ExtractArgs a
     }
 }
 
-inline bool finite_f(float x) { return x == x && x - x == 0.0f; }
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 // The volume checks every entry point shares; fills g.
 int check_volume(const char* who, const gstex_tsdf_volume& vol, Grid& g) {
     GSTEX_REQUIRE(vol.nx >= 2 && vol.ny >= 2 && vol.nz >= 2, "%s: every dim must be >= 2 (got nx=%d, ny=%d, nz=%d)",
@@ -269,7 +266,7 @@ int check_volume(const char* who, const gstex_tsdf_volume& vol, Grid& g) {
                       finite_f(vol.voxel_size) && vol.voxel_size > 0.0f,
                   "%s: the origin must be finite and voxel_size finite and > 0", who);
     GSTEX_REQUIRE(vol.tsdf && vol.weight, "%s: null volume (tsdf / weight)", who);
-    GSTEX_REQUIRE(aligned4(vol.tsdf) && aligned4(vol.weight) && aligned4(vol.color),
+    GSTEX_REQUIRE(aligned(vol.tsdf, 4) && aligned(vol.weight, 4) && aligned(vol.color, 4),
                   "%s: misaligned pointer (4-byte words)", who);
     g.nx = vol.nx; g.ny = vol.ny; g.nz = vol.nz; g.n_vox = (int)n_vox;
     g.ox = vol.origin[0]; g.oy = vol.origin[1]; g.oz = vol.origin[2]; g.h = vol.voxel_size;
@@ -281,7 +278,8 @@ int fill_extract(const char* who, const gstex_mesh_extract_args& p, ExtractArgs&
     if (rc != GSTEX_OK) return rc;
     GSTEX_REQUIRE(p.table && p.edge_mask && p.vertex_count && p.face_count,
                   "%s: null pointer (table / edge_mask / vertex_count / face_count)", who);
-    GSTEX_REQUIRE(aligned4(p.table) && aligned4(p.edge_mask) && aligned4(p.vertex_count) && aligned4(p.face_count),
+    GSTEX_REQUIRE(aligned(p.table, 4) && aligned(p.edge_mask, 4) && aligned(p.vertex_count, 4) &&
+                      aligned(p.face_count, 4),
                   "%s: misaligned pointer (4-byte words)", who);
     a.tsdf = p.vol.tsdf; a.weight = p.vol.weight; a.color = p.vol.color;
     a.table = p.table; a.edge_mask = p.edge_mask; a.vertex_count = p.vertex_count; a.face_count = p.face_count;
@@ -319,7 +317,7 @@ extern "C" int gstex_tsdf_integrate(const gstex_tsdf_integrate_args* args, void*
                       "gstex_tsdf_integrate: view %d: fx, fy must be finite and > 0, cx, cy finite", q);
         GSTEX_REQUIRE(s.cam.viewmat && s.depth && s.alpha, "gstex_tsdf_integrate: view %d: null pointer", q);
         GSTEX_REQUIRE(!p.vol.color || s.rgb, "gstex_tsdf_integrate: view %d: null rgb, which a colour volume needs", q);
-        GSTEX_REQUIRE(aligned4(s.cam.viewmat) && aligned4(s.depth) && aligned4(s.alpha) && aligned4(s.rgb),
+        GSTEX_REQUIRE(aligned(s.cam.viewmat, 4) && aligned(s.depth, 4) && aligned(s.alpha, 4) && aligned(s.rgb, 4),
                       "gstex_tsdf_integrate: view %d: misaligned pointer (4-byte words)", q);
         ViewK& k = a.v[q];
         k.viewmat = s.cam.viewmat; k.depth = s.depth; k.alpha = s.alpha; k.rgb = s.rgb;
@@ -361,8 +359,8 @@ extern "C" int gstex_mesh_extract_emit(const gstex_mesh_extract_args* args, void
     GSTEX_REQUIRE(p.n_vertices == 0 || p.vertices, "gstex_mesh_extract_emit: null vertices");
     GSTEX_REQUIRE(p.n_faces == 0 || p.faces, "gstex_mesh_extract_emit: null faces");
     GSTEX_REQUIRE(!p.colors || p.vol.color, "gstex_mesh_extract_emit: colors need a colour volume");
-    GSTEX_REQUIRE(aligned4(p.vertex_offsets) && aligned4(p.face_offsets) && aligned4(p.vertices) &&
-                      aligned4(p.colors) && aligned4(p.faces),
+    GSTEX_REQUIRE(aligned(p.vertex_offsets, 4) && aligned(p.face_offsets, 4) && aligned(p.vertices, 4) &&
+                      aligned(p.colors, 4) && aligned(p.faces, 4),
                   "gstex_mesh_extract_emit: misaligned pointer (4-byte words)");
     mesh_emit_kernel<<<div_up(a.g.n_vox, kThreads), kThreads, 0, as_stream(stream)>>>(a);
     return launch_status("gstex_mesh_extract_emit");

@@ -8,6 +8,8 @@ DESIGN.md "Mesh scoring and nearest neighbours").
                         kernel operation is one correctly rounded fp32 operation in a fixed order, so kernel and twin
                         agree bit for bit on every output the contract orders (a cell's records are a set: the order
                         inside a cell is an atomic cursor's)
+* walk_rings_eager / nn_query_walk_eager    the kernels' ring walk on the host, stated once (it also serves
+                        cluster.dbscan_walk_eager), and gstex_nn_query's kernel restated through it (tests, small sets)
 * sample_mesh           (samples, weights, face_of) of a triangle mesh on the mesh's device
 * knn_mean_dist_device  the initialisation's per-point scale, the mean distance to the k nearest other points
 
@@ -80,11 +82,11 @@ def default_cell_size(n: int, lo, hi) -> float:
 
 # ---------------------------------------------------------------------------------------- eager twins
 def _cells_eager(points, origin, cell_size, dims):
-    """(int)((p - origin) / cell_size) per axis, clamped: -> (n, 3) int64."""
+    """(int)((p - origin) / cell_size) per axis, clamped, NaN -> 0 as the kernel's fmaxf gives: -> (n, 3) int64."""
     o = torch.stack([_s(v, points) for v in origin])
     t = (points - o[None]) / _s(cell_size, points)
     top = torch.tensor([d - 1 for d in dims], dtype=torch.float32, device=points.device)
-    return torch.minimum(torch.maximum(t, torch.zeros_like(t)), top[None]).to(torch.int64)
+    return torch.minimum(torch.where(t > 0, t, torch.zeros_like(t)), top[None]).to(torch.int64)
 
 
 def grid_build_eager(points, origin, cell_size, dims):
@@ -136,30 +138,61 @@ def nn_query_eager(points, queries, k: int = 1, exclude_self: bool = False, max_
     return out_d, out_i
 
 
+def query_cell_eager(q, origin, cell_size):
+    """The unclamped cell of q (3 fp32 numbers) as the kernels' query_cell_axis gives it: per axis floor((q - o) / h)
+    in fp32, kept within +-2^29, NaN -> -2^29.  -> (cx, cy, cz) python ints."""
+    f, limit = np.float32, 2 ** 29
+    with np.errstate(all="ignore"):
+        t = [np.floor(f(f(q[c]) - f(origin[c])) / f(cell_size)) for c in range(3)]
+    return tuple(-limit if v != v else int(min(max(v, -limit), limit)) for v in t)
+
+
+def walk_rings_eager(q, origin, cell_size, dims, cell_start, scan, bound):
+    """nn_grid.h's walk_rings on the host, the one ring walk of every host twin: the Chebyshev rings of cells around
+    q's unclamped cell, from the first that meets the grid to the last, scan(a, b) for each contiguous run of records
+    cell_start[c] .. cell_start[c'] of a ring's cells (a whole row x0..x1 on a face of the ring; through its inside the
+    two end cells cx - r and cx + r where they are in the grid; ring 0: one cell, not twice), and after every ring
+    r >= 1 the stop test ((float)r * h) * (1 - 2^-10), squared, >= bound(), the fp32 squared radius still of
+    interest.  Every fp32 value is one individually rounded operation, as in the kernel."""
+    f = np.float32
+    nx, ny, nz = (int(d) for d in dims)
+    h, margin = f(cell_size), f(1.0 - 2.0 ** -10)
+    cx, cy, cz = query_cell_eager(q, origin, cell_size)
+    r_first = max(-cx, cx - (nx - 1), -cy, cy - (ny - 1), -cz, cz - (nz - 1), 0)
+    r_last = max(cx, nx - 1 - cx, cy, ny - 1 - cy, cz, nz - 1 - cz)
+    for r in range(r_first, r_last + 1):
+        x0, x1 = max(cx - r, 0), min(cx + r, nx - 1)
+        ends = [x for x in ((cx - r, cx + r) if r > 0 else (cx,)) if 0 <= x < nx]
+        for z in range(max(cz - r, 0), min(cz + r, nz - 1) + 1):
+            for y in range(max(cy - r, 0), min(cy + r, ny - 1) + 1):
+                base = (z * ny + y) * nx
+                if abs(z - cz) == r or abs(y - cy) == r:
+                    if x0 <= x1:
+                        scan(cell_start[base + x0], cell_start[base + x1 + 1])
+                else:
+                    for x in ends:
+                        scan(cell_start[base + x], cell_start[base + x + 1])
+        if r >= 1:
+            lb = f(f(r) * h) * margin
+            if lb * lb >= bound():
+                break
+
+
 def nn_query_walk_eager(origin, cell_size, dims, cell_start, records, queries, k: int = 1, exclude_self: bool = False,
                         max_radius=None):
-    """gstex_nn_query's kernel restated walk for walk on the host, one python loop per query (for tests and small
-    sets): the unclamped cell, the first and last ring, each ring's rows as the kernel segments them, the top-k under
-    (d2, index) and the stop test ((float)r * h) * (1 - 2^-10), squared, >= min(k-th best, max_radius^2) from ring 1
-    on.  -> (d2 (Q, k) f32, index (Q, k) int32), which must equal nn_query_eager's."""
+    """gstex_nn_query's kernel restated on the host, one python loop per query (for tests and small sets):
+    walk_rings_eager carrying the top-k under (d2, index), stopped on min(k-th best, max_radius^2).  -> (d2 (Q, k) f32,
+    index (Q, k) int32), which must equal nn_query_eager's."""
     f = np.float32
     rec = records.detach().cpu().numpy()
     pts, idx = rec[:, :3], np.ascontiguousarray(rec[:, 3]).view(np.int32)
     cs = cell_start.detach().cpu().numpy().astype(np.int64)
     qs = queries.detach().cpu().to(torch.float32).numpy()
-    nx, ny, nz = (int(d) for d in dims)
-    h, o = f(cell_size), [f(v) for v in origin]
     r2max = f(np.inf) if max_radius is None else f(max_radius) * f(max_radius)
-    margin, limit = f(1.0 - 2.0 ** -10), 2 ** 29
     out_d = np.full((qs.shape[0], k), np.inf, np.float32)
     out_i = np.full((qs.shape[0], k), -1, np.int32)
     for row, q in enumerate(qs):
-        with np.errstate(all="ignore"):
-            t = [np.floor(f(f(q[c] - o[c]) / h)) for c in range(3)]
-        cx, cy, cz = (-limit if v != v else int(min(max(v, -limit), limit)) for v in t)
         best = []  # (d2, index), ascending
-        r_first = max(-cx, cx - (nx - 1), -cy, cy - (ny - 1), -cz, cz - (nz - 1), 0)
-        r_last = max(cx, nx - 1 - cx, cy, ny - 1 - cy, cz, nz - 1 - cz)
 
         def scan(a, b):
             nonlocal best
@@ -172,24 +205,8 @@ def nn_query_walk_eager(origin, cell_size, dims, cell_start, records, queries, k
                     continue
                 best = sorted(best + [(dv, int(iv))])[:k]
 
-        for r in range(r_first, r_last + 1):
-            x0, x1 = max(cx - r, 0), min(cx + r, nx - 1)
-            ends = [x for x in ((cx - r, cx + r) if r > 0 else (cx,)) if 0 <= x < nx]
-            for z in range(max(cz - r, 0), min(cz + r, nz - 1) + 1):
-                z_face = abs(z - cz) == r
-                for y in range(max(cy - r, 0), min(cy + r, ny - 1) + 1):
-                    base = (z * ny + y) * nx
-                    if z_face or abs(y - cy) == r:
-                        if x0 <= x1:
-                            scan(cs[base + x0], cs[base + x1 + 1])
-                    else:
-                        for x in ends:
-                            scan(cs[base + x], cs[base + x + 1])
-            if r >= 1:
-                lb = f(f(r) * h) * margin
-                kth = best[k - 1][0] if len(best) == k else f(np.inf)
-                if lb * lb >= min(kth, r2max):
-                    break
+        walk_rings_eager(q, origin, cell_size, dims, cs, scan,
+                         lambda: min(best[k - 1][0] if len(best) == k else f(np.inf), r2max))
         for s, (dv, iv) in enumerate(best):
             out_d[row, s], out_i[row, s] = dv, iv
     return torch.from_numpy(out_d), torch.from_numpy(out_i)

@@ -119,6 +119,89 @@ def test_grid_cases_are_what_they_claim():
     assert bool(torch.isfinite(far).all()) and float(far.min()) > 50.0 ** 2
 
 
+def _walk(grid, q, scan, bound):
+    N.walk_rings_eager(np.asarray(q, np.float32), grid.origin, grid.cell_size, grid.dims,
+                       grid.cell_start.numpy().astype(np.int64), scan, bound)
+
+
+@pytest.mark.parametrize("name, row", [("tiny_cells", 4), ("boundaries", 62), ("one_cell", 0), ("far_outside", 7)])
+def test_walk_delivers_every_record_exactly_once(name, row):
+    """walk_rings_eager on its own, never stopped (bound = +inf): the runs it delivers, concatenated, hold every record
+    index of [0, n) exactly once -- each ring's cells once, no cell twice, none missed.  One query of the case's own
+    per grid: between the points of the plane and off it (tiny_cells: about fifty rings, the first ones empty), the
+    lattice's centre (boundaries: rings with rows through their inside), inside the only cell, and 1e6 away."""
+    c = NC.grid_cases()[name]
+    grid = N.PointGrid(c["points"], cell_size=c["cell_size"])
+    if name == "far_outside":
+        assert c["queries"][row].tolist() == [1e6, -1e6, 1e6]
+    runs = []
+    _walk(grid, c["queries"][row].numpy(), lambda a, b: runs.append((int(a), int(b))), lambda: np.float32(np.inf))
+    assert all(0 <= a <= b <= grid.n for a, b in runs)
+    seen = np.concatenate([np.arange(a, b) for a, b in runs])
+    assert seen.shape[0] == grid.n and (np.sort(seen) == np.arange(grid.n)).all()
+
+
+def test_walk_stops_on_its_bound():
+    """radius_cuts_2_3 with the fixed bound r2 = 2 * 2 (fp32): once a ring r >= 1 has ((float)r h)(1 - 2^-10), squared,
+    >= r2, no further run is delivered, and every point within r2 of the query lies in a delivered run.  bound() is
+    called once after each ring r >= 1, which numbers the rings from the first one (query_cell_eager is the
+    walker's own cell)."""
+    f = np.float32
+    c = NC.grid_cases()["radius_cuts_2_3"]
+    grid = N.PointGrid(c["points"], cell_size=c["cell_size"])
+    q = c["queries"][0].numpy()
+    r2 = f(2.0) * f(2.0)
+    cell = N.query_cell_eager(q, grid.origin, grid.cell_size)
+    r_first = max(max(-v, v - (d - 1), 0) for v, d in zip(cell, grid.dims))
+    state = {"r": max(r_first, 1), "stopped": False}
+    runs = []
+
+    def scan(a, b):
+        assert not state["stopped"], f"a run of ring {state['r']} after the bound was reached"
+        runs.append((int(a), int(b)))
+
+    def bound():
+        lb = f(f(state["r"]) * f(grid.cell_size)) * f(1.0 - 2.0 ** -10)
+        state["stopped"] = bool(lb * lb >= r2)
+        state["r"] += 1
+        return r2
+
+    _walk(grid, q, scan, bound)
+    assert state["stopped"]  # the walk ended on the test, not on the grid's last ring
+    seen = set(int(i) for a, b in runs for i in range(a, b))
+    assert len(seen) < grid.n
+    rec = grid.records.numpy()
+    d = q[None] - rec[:, :3]
+    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    within = set(np.nonzero(d2 <= r2)[0].tolist())
+    assert len(within) == 2 and within <= seen
+
+
+def test_walk_cell_rule_and_the_cluster_twin():
+    """A NaN coordinate gives the cell -2^29 and one at 1e30 the cell +2^29 on that axis, and the walk of such a query
+    returns.  dbscan_walk_eager has the rule from the shared walker: with one mean NaN it returns, that splat noise (a
+    NaN query passes no d2 <= eps test, and no other record's scan admits the NaN record), as the kernels give."""
+    import cluster_cases as CC
+    from gstex_amd import cluster as C
+
+    c = NC.grid_cases()["one_cell"]
+    grid = N.PointGrid(c["points"], cell_size=c["cell_size"])
+    q = np.array([float("nan"), 0.5, 1e30], np.float32)
+    assert N.query_cell_eager(q, grid.origin, grid.cell_size) == (-2 ** 29, 0, 2 ** 29)
+    for bad in (np.array([float("nan"), 0.5, 0.5], np.float32), np.array([0.5, 0.5, 1e30], np.float32)):
+        runs = []
+        _walk(grid, bad, lambda a, b: runs.append((int(a), int(b))), lambda: np.float32(np.inf))
+        assert runs == [(0, grid.n)]
+    s = CC.cases()["two_blobs_noise"]
+    means = s["means"].clone()
+    means[17, 1] = float("nan")
+    got = C.dbscan_walk_eager(means, s["scales"], s["quats"], s["eps"], 5)
+    assert int(got.labels[17]) == -1 and int(got.degree[17]) == 0
+    want = C.dbscan_eager(means, s["scales"], s["quats"], s["eps"], 5)
+    assert torch.equal(got.labels, want.labels) and torch.equal(got.degree, want.degree)
+    assert got.n_clusters == want.n_clusters >= 2
+
+
 def test_default_cell_size_and_limits():
     P, _ = NC.random_case()
     grid = N.PointGrid(P)

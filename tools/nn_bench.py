@@ -3,8 +3,8 @@
 
 Times, on points sampled near a surface (a bumpy sphere with 0.2 % noise, the shape of a scan or of mesh samples):
   * PointGrid(points): the build (bounds read-back, count, scan, place);
-  * PointGrid.query(queries, k=1): the queries ordered by cell (count, scan, place on them) and gstex_nn_query; and the
-    gstex_nn_query launch alone on ordered and on unordered queries;
+  * PointGrid.query(queries, k) for --k neighbours: the queries ordered by cell (count, scan, place on them) and
+    gstex_nn_query; and the gstex_nn_query launch alone on ordered and on unordered queries;
   * knn_mean_dist_device at --knn-points uniform points in a cube (the initialisation's case);
 against scipy's cKDTree on this machine's host (build, and query with workers=16), which is what users have without
 it.  --cell-scales sweeps the cell size around the default.  Wall-clock around a device synchronisation for the
@@ -66,6 +66,7 @@ def main():
     ap.add_argument("--queries", type=int, default=1_000_000)
     ap.add_argument("--knn-points", type=int, default=200_000)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--k", type=int, default=1, help="neighbours per query (1..8)")
     ap.add_argument("--cell-scales", type=str, default="1")
     ap.add_argument("--workers", type=int, default=16)
     ap.add_argument("--skip-host", action="store_true")
@@ -77,8 +78,8 @@ def main():
     dev = torch.device("cuda", 0)
     P, Q = surface_points(args.points, 1), surface_points(args.queries, 2)
     Pd, Qd = P.to(dev), Q.to(dev)
-    res = {"points": args.points, "queries": args.queries, "knn_points": args.knn_points, "reps": args.reps,
-           "workers": args.workers}
+    res = {"points": args.points, "queries": args.queries, "k": args.k, "knn_points": args.knn_points,
+           "reps": args.reps, "workers": args.workers}
     N.PointGrid(Pd).query(Qd[:1000])  # warm-up: library load, allocator
     base = N.PointGrid(Pd)
     sweep = []
@@ -86,11 +87,12 @@ def main():
     for scale in [float(s) for s in args.cell_scales.split(",")]:
         h = base.cell_size * scale
         build_ms, grid = wall(lambda: N.PointGrid(Pd, cell_size=h), args.reps)
-        query_ms, (d2, _) = wall(lambda: grid.query(Qd, k=1), args.reps)
+        query_ms, (d2, _) = wall(lambda: grid.query(Qd, k=args.k), args.reps)
         _, qrec = N.grid_build(Qd, grid.origin, grid.cell_size, grid.dims)
         plain = torch.cat([Qd, torch.arange(Qd.shape[0], device=dev, dtype=torch.int32).view(torch.float32)[:, None]],
                           1).contiguous()
-        launch = lambda q: N.nn_query(grid.origin, grid.cell_size, grid.dims, grid.cell_start, grid.records, q)  # noqa: E731
+        launch = lambda q: N.nn_query(grid.origin, grid.cell_size, grid.dims, grid.cell_start, grid.records, q,  # noqa: E731
+                                      k=args.k)
         cells = grid.dims[0] * grid.dims[1] * grid.dims[2]
         occupied = int((grid.cell_start[1:] > grid.cell_start[:-1]).sum())
         sweep.append({"cell_scale": scale, "cell_size": grid.cell_size, "dims": grid.dims, "cells": cells,
